@@ -1,11 +1,18 @@
 """Benchmark of the aggregation hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload colwise|krum|bulyan|step [--gar RULE]]
+    python bench.py --gpus N --steps K --warmup W [--workload colwise|krum|bulyan|step [--gar RULE]] [--full]
+                    [--dump-outputs DIR]
+
+A plain run measures the headline alone: it sets up, warms up, times the K steps, writes its outputs if --dump-outputs
+is given, and prints the JSON line (`ms_per_step` = wall-clock milliseconds of one timed step).  Everything else
+described below — side entries, exchange legs, CPU baselines, live traffic passes — runs only with --full.
+--dump-outputs DIR: what the timed path returned in its last step, as DIR/<name>.npy (dump_outputs); the inputs are
+seeded, so two builds of the project run with the same arguments can be compared output for output.
 
 N = 1 (default): BASELINE.json configs[1] — coordinate-wise median + trimmed mean (f=5) over a synthetic
 stack of n=25 worker gradients x d=11 173 962 coordinates (ResNet-18-sized), fp32, inputs resident in
 HBM.  One "step" = one pass of the path over one batch = one median + one trimmed-mean aggregation;
-`value` = aggregations per second.  The same line carries, under `per_gar`, short measurements of the
+`value` = aggregations per second.  With --full the same line carries, under `per_gar`, short measurements of the
 other single-GPU configurations (C3 Multi-Krum n=51, C4 Bulyan n=25, C5 full step at d=36.5 M), each
 with its algorithmic bytes and fraction of the 8 TB/s HBM roofline (skip with --no-extras).
 
@@ -14,8 +21,8 @@ torchrun launch is used as is): the SAME workload, the gradient dimension partit
 holds a shard of 11 173 962 coordinates of the n = 25 gradients of an N x 11 173 962-coordinate vector ("weak" scaling:
 the work per GPU is that of the one-GPU line).  The coordinate-wise rules are independent per coordinate, so this
 path has no exchange step and no collective is issued inside the timed region; `value` = aggregations of an
-n = 25 x d = 11 173 962 stack per second over all ranks (the unit of the one-GPU line).  The path's one real exchange
-is measured in the same run, under `per_gar`: BASELINE.json configs[3] — Bulyan n=25, f=5 over a FIXED total
+n = 25 x d = 11 173 962 stack per second over all ranks (the unit of the one-GPU line).  With --full the path's one real
+exchange is measured in the same run, under `per_gar`: BASELINE.json configs[3] — Bulyan n=25, f=5 over a FIXED total
 d = 11 173 962 split across the ranks by shard_bounds ("strong" scaling), with the all-reduce of the 25x25 fp64
 squared-distance partials over RCCL inside the timed call (`bulyan_c4_sharded`, next to `single_gpu_same_workload`,
 the unsharded rule timed on rank 0 alone), the optional all-gather of the output, and the worker-parallel layout
@@ -24,7 +31,7 @@ unless --scaling weak).
 
 The JSON line also carries `roofline` (algorithmic bytes / HIP-event time of the dominant kernel vs
 8 TB/s; `traffic` = HBM bytes per launch from rocprofv3 FETCH_SIZE/WRITE_SIZE passes of this very
-command, collected live unless --no-traffic) and `cpu_baseline` (the reference's own
+command, collected live under --full unless --no-traffic) and, under --full, `cpu_baseline` (the reference's own
 aggregators — the staged checkout of scripts/stage_reference.sh — or, without one, the oracle's pinned f32 port, on this
 box's host cores, rank 0, N = 1 only; full-size stacks, nothing extrapolated).
 """
@@ -76,15 +83,23 @@ def parse():
                       "+3 %% on the column kernels in round 3 and is reported as a side entry (per_gar.*_slab_rows).")
   p.add_argument("--separate-rows", action="store_true", help="(the default since round 4; kept for old command lines)")
   p.add_argument("--sharded-extras", action="store_true",
-                 help="one rank under torch.distributed.run: run the per_gar legs of the N > 1 line (sharded Bulyan with "
+                 help="with --full, one rank under torch.distributed.run: run the per_gar legs of the N > 1 line (sharded Bulyan with "
                       "its all-reduce, all-gather, layout exchange) as well, so that their code is exercised on one GPU")
   p.add_argument("--extras-timeout", type=float, default=180.0,
                  help="N > 1: seconds the exchange legs that follow the timed headline (the library's own RCCL communicator, the "
                       "sharded rule, all-gather, layout exchange) may take on every rank before the line is printed without them "
                       "(`exchange.error`) and the job ends: a hang there must not cost the headline (0 = no limit)")
   p.add_argument("--graph-replay", action="store_true",
-                 help="N > 1 (or one rank under torch.distributed.run): also time the sharded rule recorded into a HIP "
+                 help="with --full, N > 1 (or one rank under torch.distributed.run): also time the sharded rule recorded into a HIP "
                       "graph, one graph per synthetic stack (byzantinemomentum_amd/graphs.py) -> per_gar.<rule>_graph_replay")
+  p.add_argument("--full", action="store_true",
+                 help="also measure what the headline does not need: the per_gar side entries of C3/C4/C5, the CPU "
+                      "baselines, the live rocprofv3 traffic passes and, under torch.distributed.run, the exchange legs "
+                      "(--no-extras, --no-cpu-baseline and --no-traffic switch single legs off again).  Default: the headline alone")
+  p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                 help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy "
+                      "(float32 / float64, at most 64 MB in all: a larger output is written as a fixed, seeded sample of "
+                      "its coordinates), for comparing two builds output for output")
   p.add_argument("--aliased-byz", action="store_true",
                  help="make the f Byzantine rows ONE aliased tensor as the reference's attacks do "
                       "(attacks/identical.py:86); they are then served from cache and the HBM traffic "
@@ -201,6 +216,37 @@ def timed_loop(fn, steps, warmup, timer, name):
   return timer.mean_ms(name)
 
 
+DUMP_BYTES = 64 * 1000 * 1000  # --dump-outputs: every file of one run together, headers included
+
+
+def dump_outputs(directory, outputs, rank=0, world=1):
+  """--dump-outputs: what the timed path returned in its last step, one DIR/<name>.npy per array — float64 where the path
+  returns double precision (the step's statistics, Python floats: one-element arrays), float32 otherwise.  The small
+  outputs are written whole; an output larger than its share of what is left of DUMP_BYTES is written as a fixed sample
+  of its coordinates: the sorted indices numpy.random.default_rng(0).choice(size, k, replace=False), the same in every
+  run and every build, so that two builds compare coordinate for coordinate.  With more than one rank every rank writes its own shard as <name>.rank<r>.npy."""
+  import numpy as np
+  os.makedirs(directory, exist_ok=True)
+  arrays = {}
+  for name, val in outputs.items():
+    if isinstance(val, torch.Tensor):
+      t = val.detach().reshape(-1)
+      arrays[name] = (t if t.dtype == torch.float64 else t.float()).cpu().numpy()
+    else:
+      arrays[name] = np.asarray([val], dtype=np.float64)
+  left = DUMP_BYTES // world - 128 * len(arrays)  # (128: an .npy header)
+  picks = {}
+  for count, name in enumerate(sorted(arrays, key=lambda nm: (arrays[nm].nbytes, nm))):
+    a = arrays[name]
+    k = min(a.size, left // (len(arrays) - count) // a.itemsize)  # the small outputs whole, the rest shared evenly
+    left -= k * a.itemsize
+    if a.size > k:
+      if (a.size, k) not in picks:
+        picks[(a.size, k)] = np.sort(np.random.default_rng(0).choice(a.size, k, replace=False))
+      a = a[picks[(a.size, k)]]
+    np.save(os.path.join(directory, f"{name}.npy" if world == 1 else f"{name}.rank{rank}.npy"), a)
+
+
 # ---------------------------------------------------------------------------- #
 # CPU baseline (rank 0, one GPU only): the oracle's f32 port = the reference's torch-CPU operations
 
@@ -224,9 +270,9 @@ def _pick_threads(fn):
 
 
 def _cpu_reference():
-  """The reference's own registry (`aggregators.gars`) when a checkout is importable — /root/reference in the build
-  container, the staged oracle/_ref/reference (scripts/stage_reference.sh) on the GPU box — else None: the oracle's
-  f32 port, pinned bit-identical to it by tests/test_oracle_vs_reference.py, is timed instead (kind "port")."""
+  """The reference's own registry (`aggregators.gars`) when a checkout is importable — the one build() staged under
+  oracle/_ref/reference (scripts/stage_reference.sh) — else None: the oracle's f32 port, pinned bit-identical to it by
+  tests/test_oracle_vs_reference.py, is timed instead (kind "port")."""
   from oracle import reference_loader
   if not reference_loader.available():
     return None
@@ -348,7 +394,7 @@ def measure_traffic(argv, kernel_substrings, extras=False):
     with tempfile.TemporaryDirectory(dir="/tmp") as tmp:
       cmd = [exe, "--pmc", counter, "--kernel-trace", "--output-format", "csv", "-d", tmp, "-o", "pmc", "--",
              sys.executable, str(ROOT / "bench.py"), *argv, "--steps", "4", "--warmup", "1", "--no-cpu-baseline",
-             "--no-traffic"] + ([] if extras else ["--no-extras"])
+             "--no-traffic"] + (["--full"] if extras else [])
       try:
         subprocess.run(cmd, cwd="/tmp", env=env, capture_output=True, timeout=420, check=True)
       except Exception:  # noqa: BLE001
@@ -661,8 +707,8 @@ def main():
     def step(i, timed):
       st = stacks[i & 1]
       if timed:
-        timer.run("median", lambda: bm.median(st))
-        timer.run("trmean", lambda: bm.trmean(st, f))
+        return {"median": timer.run("median", lambda: bm.median(st)),
+                "trmean": timer.run("trmean", lambda: bm.trmean(st, f))}
       else:
         bm.median(st)
         bm.trmean(st, f)
@@ -686,7 +732,8 @@ def main():
 
     def step(i, timed):
       if timed:
-        timer.run("step", lambda: (runner.run(sets[i & 1]), runner.floats()))
+        defense, floats = timer.run("step", lambda: (runner.run(sets[i & 1]), runner.floats()))
+        return dict({"defense": defense}, **{f"stat_{k}": v for k, v in floats.items()})
       else:
         runner.run(sets[i & 1])
         runner.floats()
@@ -706,7 +753,7 @@ def main():
       st = stacks[i & 1]
       bm.gars.invalidate_rank_cache()  # (every call runs its distance pass: see timed_loop)
       if timed:
-        timer.run(workload, lambda: rule(st, f))
+        return {workload: timer.run(workload, lambda: rule(st, f))}
       else:
         rule(st, f)
     workload_name = (f"{'C3 multi-krum' if workload == 'krum' else 'C4 bulyan'}: n={n}, f={f}, m={m}, total d={d_total}"
@@ -717,11 +764,18 @@ def main():
   for i in range(max(args.warmup, 27) if workload == "step" else args.warmup):  # step: fill the deque of 25 pasts
     step(i, False)
   barrier()
+  outputs = None
   t0 = time.perf_counter()
   for i in range(args.steps):
-    step(i, True)
+    if args.dump_outputs is not None and i == args.steps - 1:
+      outputs = step(i, True)  # (only the last step's: the others are dropped at once, as without the option)
+    else:
+      step(i, True)
   barrier()
   elapsed = time.perf_counter() - t0
+  if outputs is not None:
+    dump_outputs(args.dump_outputs, outputs, rank, world)
+    del outputs
   if distributed:
     t = torch.tensor([elapsed], dtype=torch.float64, device=device)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -780,11 +834,11 @@ def main():
   # did not need one) and runs collectives no single-GPU box can exercise with real peers: under a deadline, so that a
   # failure there costs the `exchange` object of the line and not the line.
   cpu_sample = None
-  if world == 1 and rank == 0 and not args.no_cpu_baseline and workload in ("bulyan", "krum"):
+  if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline and workload in ("bulyan", "krum"):
     cpu_sample = _host_copy(stacks[0])  # (the device stacks go before the extras run)
   exchange_rule = (workload if workload in ("bulyan", "krum") else
                    "bulyan" if workload == "colwise" and not args.no_extras and (world > 1 or args.sharded_extras) else None)
-  if distributed and exchange_rule is not None:
+  if args.full and distributed and exchange_rule is not None:
     del stacks
     stacks = None
     torch.cuda.empty_cache()
@@ -826,7 +880,9 @@ def main():
       os._exit(0)
 
   # ---- N = 1: the other single-GPU configurations, briefly ----
-  if world == 1 and workload == "colwise" and not args.no_extras and rank == 0 and stacks is not None:
+  if not args.full:
+    pass  # a plain run: the headline alone
+  elif world == 1 and workload == "colwise" and not args.no_extras and rank == 0 and stacks is not None:
     first = stacks[0]
     if not args.no_cpu_baseline:
       extra["cpu_baseline"] = cpu_baseline_colwise(first, f)
@@ -843,7 +899,7 @@ def main():
     dominant = max(algo_bytes, key=lambda k: per_gar[k]["avg_ms"])
     traffic, per_kernel = None, None
     # (not under torch.distributed.run: the child processes would inherit the launcher's rendezvous environment)
-    if world == 1 and not distributed and not args.no_traffic and "BM_BENCH_CHILD" not in os.environ:
+    if args.full and world == 1 and not distributed and not args.no_traffic and "BM_BENCH_CHILD" not in os.environ:
       child = ["--workload", workload, "--gar", args.gar] + (["--d", str(args.d)] if args.d else []) + \
           (["--aliased-byz"] if args.aliased_byz else [])
       with_extras = workload == "colwise" and not args.no_extras and args.d is None

@@ -1,12 +1,11 @@
 """Import the REAL reference to validate the oracle, to generate the golden fixtures and — staged —
 as the CPU reference on the GPU box.  TEST INFRASTRUCTURE: the product never imports this.
 
-Two places hold a checkout: /root/reference (the build container, read-only) and the git-ignored
-oracle/_ref/reference that `scripts/stage_reference.sh` fills from it (`__graft_entry__.build()` runs
-the recipe whenever /root/reference is present).  The staged copy rides the gpurun snapshot, so the
-`-m gpu` tests that drive the unmodified attack.py, the full-size fp32 parity tests and bench.py's
-`cpu_baseline` leg (kind "reference") find the reference's own code on the GPU box; none of them reads
-/root/reference at run time.
+The checkout read here is the git-ignored oracle/_ref/reference that `scripts/stage_reference.sh` fills
+(`__graft_entry__.build()` runs the recipe whenever a reference checkout is on the build machine), or
+the directory named by BM_REFERENCE_DIR.  Nothing outside the repository is read at test time: the
+`-m gpu` tests that drive the unmodified attack.py, the full-size fp32 parity tests, the `reference`
+tests and bench.py's `cpu_baseline` leg (kind "reference") all find the reference's own code there.
 
 The reference's `tools` package wraps sys.stdout/sys.stderr and replaces sys.excepthook at import
 (tools/__init__.py:215-246); we restore them so pytest's capture keeps working.
@@ -20,10 +19,10 @@ STAGED_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_ref", "r
 
 def _find():
   env = os.environ.get("BM_REFERENCE_DIR")
-  for cand in ([env] if env else []) + ["/root/reference", STAGED_DIR]:
+  for cand in ([env] if env else []) + [STAGED_DIR]:
     if os.path.isfile(os.path.join(cand, "aggregators", "__init__.py")):
       return cand
-  return env or "/root/reference"
+  return env or STAGED_DIR
 
 
 REFERENCE_DIR = _find()

@@ -40,7 +40,7 @@ case $name in
     tail -1 $out/hunt_shipped.jsonl | cut -c1-900
     for side in new old new old; do
       lib=""; [ $side = old ] && lib=scratch/slp/libbm_gar_r5flags.so
-      BM_GAR_LIB=$lib timeout 600 python bench.py > $out/bench_${side}_$(date +%s).json 2>> $out/bench.err
+      BM_GAR_LIB=$lib timeout 600 python bench.py --full > $out/bench_${side}_$(date +%s).json 2>> $out/bench.err
     done
     for i in 1 2 3; do
       BM_TEST_POISON=0 timeout 500 python -m pytest tests/test_gpu_full_size_o1.py tests/test_gpu_zz_multirank.py -m gpu -q > $out/pair_$i.log 2>&1
@@ -60,17 +60,17 @@ case $name in
     done
     timeout 300 python scripts/n51_probe.py > $out/n51_probe.txt 2>&1; cat $out/n51_probe.txt
     scripts/pmc_collect.sh $out n51 -- python scripts/n51_probe.py 3 > $out/n51_pmc.txt 2>&1; tail -3 $out/n51_pmc.txt
-    for i in 1 2; do timeout 600 python bench.py > $out/bench_$i.json 2> $out/bench_$i.err; wc -c $out/bench_$i.json; done
+    for i in 1 2; do timeout 600 python bench.py --full > $out/bench_$i.json 2> $out/bench_$i.err; wc -c $out/bench_$i.json; done
     ;;
   round3)   # the static window search / Aksel lane pointers: n = 51 again, the whole suite, the bench
     timeout 300 python scripts/n51_probe.py > $out/n51_probe.txt 2>&1; cat $out/n51_probe.txt
     ( time timeout 1800 python -m pytest tests -m gpu -x -q ) > $out/pytest_gpu.log 2>&1; tail -4 $out/pytest_gpu.log
-    timeout 600 python bench.py > $out/bench_1.json 2> $out/bench_1.err; wc -c $out/bench_1.json
+    timeout 600 python bench.py --full > $out/bench_1.json 2> $out/bench_1.err; wc -c $out/bench_1.json
     ;;
   round4)   # Aksel forms A/B at n = 51, the whole suite, the bench
     for lanes in 0 1 2 0 1 2; do echo "BM_AKSEL_LANES=$lanes"; BM_AKSEL_LANES=$lanes timeout 300 python scripts/n51_probe.py 2>&1 | grep -v amdgpu.ids; done > $out/n51_probe_aksel_forms.txt; grep "LANES\|aksel" $out/n51_probe_aksel_forms.txt
     ( time timeout 1800 python -m pytest tests -m gpu -x -q ) > $out/pytest_gpu.log 2>&1; tail -4 $out/pytest_gpu.log
-    timeout 600 python bench.py > $out/bench_1.json 2> $out/bench_1.err; wc -c $out/bench_1.json
+    timeout 600 python bench.py --full > $out/bench_1.json 2> $out/bench_1.err; wc -c $out/bench_1.json
     ;;
   round5)   # the sliced Gram reduction: suite, kernel traces of C4 / C3, the per-rank probe, bench twice, then the round-5 failing pair N times
     ( time timeout 1800 python -m pytest tests -m gpu -x -q ) > $out/pytest_gpu.log 2>&1; tail -4 $out/pytest_gpu.log
@@ -80,7 +80,7 @@ case $name in
       find $out/trace_$w -name "*kernel_trace.csv" -size +20M -delete
     done
     timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29531 scripts/per_rank_probe.py > $out/per_rank_probe.txt 2>&1; tail -12 $out/per_rank_probe.txt
-    for i in 1 2; do timeout 600 python bench.py > $out/bench_$i.json 2> $out/bench_$i.err; wc -c $out/bench_$i.json; done
+    for i in 1 2; do timeout 600 python bench.py --full > $out/bench_$i.json 2> $out/bench_$i.err; wc -c $out/bench_$i.json; done
     for i in $(seq 1 ${PAIR_RUNS:-8}); do
       BM_TEST_POISON=0 timeout 500 python -m pytest tests/test_gpu_full_size_o1.py tests/test_gpu_zz_multirank.py -m gpu -q > $out/pair_$i.log 2>&1
       tail -1 $out/pair_$i.log
@@ -144,11 +144,11 @@ case $name in
     ;;
   stallprobe)   # the one slow search in ten of the bench's first series: where does it wait?
     timeout 600 python scripts/search_stall_probe.py 2>&1 | grep -v amdgpu.ids > $out/search_stall_probe.txt; cat $out/search_stall_probe.txt | cut -c1-700
-    timeout 600 python bench.py --no-cpu-baseline --no-traffic > $out/bench_quick.json 2> $out/bench_quick.err; python -c "import json; b=json.load(open('$out/bench_quick.json')); a=b['per_gar']['attack_search_c3_krum']; print('bench without the PMC children and the CPU baselines:', a['scalar_form_each_ms'], a['host_scalar_form_each_ms'])"
+    timeout 600 python bench.py --full --no-cpu-baseline --no-traffic > $out/bench_quick.json 2> $out/bench_quick.err; python -c "import json; b=json.load(open('$out/bench_quick.json')); a=b['per_gar']['attack_search_c3_krum']; print('bench without the PMC children and the CPU baselines:', a['scalar_form_each_ms'], a['host_scalar_form_each_ms'])"
     ;;
   stallbench)   # which leg of the default bench run brings the slow search: the CPU baselines or the PMC children?
     for flag in --no-traffic --no-cpu-baseline; do
-      timeout 900 python bench.py $flag > $out/bench$flag.json 2> $out/bench$flag.err
+      timeout 900 python bench.py --full $flag > $out/bench$flag.json 2> $out/bench$flag.err
       python -c "import json; b=json.load(open('$out/bench$flag.json')); a=b['per_gar']['attack_search_c3_krum']; print('bench $flag:', a['scalar_form_each_ms'], a['host_scalar_form_each_ms'])"
     done
     ;;
@@ -171,7 +171,7 @@ case $name in
   libab)  # the in-tree library against the kernels of the ABI 22 tree (scratch/old/libbm_gar_abi22_kernels.so: scratch/abi22/build.py), whole default bench lines alternating
     for side in new old new old; do
       lib=""; [ $side = old ] && lib=scratch/old/libbm_gar_abi22_kernels.so
-      BM_GAR_LIB=$lib timeout 600 python bench.py ${LIBAB_FLAGS---no-cpu-baseline --no-traffic} > $out/bench_${side}_$(date +%s).json 2>> $out/bench.err
+      BM_GAR_LIB=$lib timeout 600 python bench.py --full ${LIBAB_FLAGS---no-cpu-baseline --no-traffic} > $out/bench_${side}_$(date +%s).json 2>> $out/bench.err
     done
     OUT=$out python - <<'PY' | tee $out/summary.txt
 import glob, json, os
@@ -227,7 +227,7 @@ PY
     timeout 600 python scripts/cursor_forms_probe.py 2>&1 | grep -v amdgpu.ids > $out/cursor_forms.txt; cat $out/cursor_forms.txt | cut -c1-400
     ( time timeout 1800 python -m pytest tests -m gpu -x -q ) > $out/pytest_gpu.log 2>&1; tail -4 $out/pytest_gpu.log
     timeout 200 python __graft_entry__.py smoke > $out/smoke.log 2>&1; tail -1 $out/smoke.log
-    timeout 600 python bench.py > $out/bench_default.json 2> $out/bench_default.err; wc -c $out/bench_default.json
+    timeout 600 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err; wc -c $out/bench_default.json
     rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_headline -o trace -- python bench.py --no-extras --no-cpu-baseline --no-traffic --steps 20 > $out/trace_headline.json 2> $out/trace_headline.err
     f=$(find $out/trace_headline -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $out/headline_kernel_stats.csv && head -6 $out/headline_kernel_stats.csv | cut -c1-200
     find $out/trace_headline -name "*kernel_trace.csv" -size +20M -delete
@@ -235,7 +235,7 @@ PY
   suite)  # what the driver runs at the end of a round
     ( time timeout 1500 python -m pytest tests -m gpu -x -q ) > $out/pytest_gpu.log 2>&1; tail -4 $out/pytest_gpu.log
     timeout 200 python __graft_entry__.py smoke > $out/smoke.log 2>&1; tail -1 $out/smoke.log
-    timeout 600 python bench.py > $out/bench_default.json 2> $out/bench_default.err; wc -c $out/bench_default.json
+    timeout 600 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err; wc -c $out/bench_default.json
     ;;
   *)      # anything else: the rest of the command line, logged (an unknown recipe name with nothing behind it is an error)
     [ $# -gt 0 ] || { echo "unknown recipe: $name"; exit 64; }

@@ -10,7 +10,7 @@ if ROOT not in sys.path:
 
 def pytest_configure(config):
   config.addinivalue_line("markers", "gpu: needs a real MI355X (run with `-m gpu` on the GPU box)")
-  config.addinivalue_line("markers", "reference: needs the read-only reference checkout at /root/reference")
+  config.addinivalue_line("markers", "reference: needs the reference checkout that build() stages under oracle/_ref/")
 
 
 def pytest_sessionstart(session):
@@ -27,7 +27,7 @@ def pytest_collection_modifyitems(config, items):
   import torch
   from oracle import reference_loader
   skip_gpu = pytest.mark.skip(reason="no GPU visible")
-  skip_ref = pytest.mark.skip(reason="reference checkout not present (GPU box)")
+  skip_ref = pytest.mark.skip(reason="no reference checkout staged under oracle/_ref/")
   has_gpu = torch.cuda.is_available()
   has_ref = reference_loader.available()
   for item in items:

@@ -164,3 +164,40 @@ def test_entries_name_their_held_up_calls():
   assert stalled["held_up_calls"] == 1 and stalled["timed_calls"] == 12 and stalled["slowest_ms"] == 40.0
   assert stalled["median_ms"] == 0.70 and stalled["avg_ms"] > 3.9
   assert stalled["frac_of_8TBps_median"] > 0.7 > 0.2 > stalled["frac_of_8TBps"]
+
+
+def test_full_is_off_by_default(monkeypatch):
+  """A plain run is the headline alone: the side measurements need --full, outputs are written only when asked for."""
+  bench = load_bench()
+  monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+  args = bench.parse()
+  assert args.full is False and args.dump_outputs is None and args.steps == 7 and args.warmup == 2
+  monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+  args = bench.parse()
+  assert args.full is True and args.dump_outputs == "out"
+
+
+def test_dump_outputs_is_bounded_and_the_same_every_run(tmp_path):
+  """--dump-outputs at the headline's size: two d = 11 173 962 fp32 outputs do not fit 64 MB together, so each is written
+  as the same seeded sample of its coordinates in every run; double precision and Python floats stay float64."""
+  import numpy as np
+  import torch
+  bench = load_bench()
+  gen = torch.Generator().manual_seed(3)
+  d = bench.D_RESNET18
+  outputs = {"median": torch.randn(d, generator=gen), "trmean": torch.randn(d, generator=gen),
+             "small": torch.arange(10, dtype=torch.float64), "stat_norm": 2.5}
+  for run in ("a", "b"):
+    bench.dump_outputs(str(tmp_path / run), outputs)
+  files = sorted(p.name for p in (tmp_path / "a").iterdir())
+  assert files == ["median.npy", "small.npy", "stat_norm.npy", "trmean.npy"]
+  assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= 64 * 1000 * 1000
+  for name in files:
+    a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+    assert a.dtype == b.dtype and np.array_equal(a, b), name
+  med = np.load(tmp_path / "a" / "median.npy")
+  assert med.dtype == np.float32 and d // 2 < med.size < d
+  assert np.isin(med, outputs["median"].numpy()).all()               # a sample of the output, not something else
+  assert np.load(tmp_path / "a" / "small.npy").tolist() == list(range(10))
+  stat = np.load(tmp_path / "a" / "stat_norm.npy")
+  assert stat.dtype == np.float64 and stat.tolist() == [2.5]

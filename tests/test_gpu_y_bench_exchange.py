@@ -31,8 +31,8 @@ def _launch(*flags, timeout=420, **environ):
 
 
 def test_one_rank_launcher_run_fills_the_exchange_object():
-  done, lines = _launch("--workload", "bulyan", "--dim", "2000003", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
-                        "--no-traffic")
+  done, lines = _launch("--workload", "bulyan", "--dim", "2000003", "--steps", "3", "--warmup", "1", "--full",
+                        "--no-cpu-baseline", "--no-traffic")
   assert done.returncode == 0, done.stderr[-3000:]
   assert len(lines) == 1, done.stdout[-2000:]
   line = json.loads(lines[0])
@@ -51,8 +51,8 @@ def test_one_rank_launcher_run_fills_the_exchange_object():
 def test_a_deadline_that_fires_costs_the_exchange_legs_not_the_line():
   # (the rank hangs for 60 s where the exchange legs start — what a peer lost in a collective looks like — with a
   #  deadline of 2 s: the line must come from the deadline, with the headline and the reason)
-  done, lines = _launch("--workload", "bulyan", "--dim", "2000003", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
-                        "--no-traffic", "--extras-timeout", "2", BM_BENCH_STALL_S="60")
+  done, lines = _launch("--workload", "bulyan", "--dim", "2000003", "--steps", "3", "--warmup", "1", "--full",
+                        "--no-cpu-baseline", "--no-traffic", "--extras-timeout", "2", BM_BENCH_STALL_S="60")
   assert done.returncode == 0, done.stderr[-3000:]
   assert len(lines) == 1, done.stdout[-2000:]
   line = json.loads(lines[0])

@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from oracle import gar_oracle as O
+from oracle import reference_loader
 from tests.golden_io import CASES, Golden
 
 
@@ -198,7 +199,7 @@ def test_reference_discovers_native_package():
           "print(','.join(names))\n"
           "assert aggregators.gars['native-aksel'].influence is not None\n"
           "assert aggregators.gars['native-trmean'].check(gradients=[1], f=1) is not None\n")
-  env = dict(os.environ, PYTHONPATH=os.pathsep.join([root, "/root/reference"]))
+  env = dict(os.environ, PYTHONPATH=os.pathsep.join([root, reference_loader.REFERENCE_DIR]))
   out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, cwd="/tmp")
   assert out.returncode == 0, out.stderr
   names = out.stdout.strip().splitlines()[-1].split(",")
