@@ -16,6 +16,7 @@ import torch
 
 from oracle import gar_oracle as O
 from tests.golden_io import CASES, Golden, same_bits
+from tests.instance_matrix import sorted_window, window_candidates as _window_candidates
 
 pytestmark = pytest.mark.gpu
 
@@ -193,20 +194,6 @@ def test_accuracy_gate_hands_over_to_the_direct_kernel():
 # ---------------------------------------------------------------------------- #
 # phocas / meamed: no exempt columns — an exact deviation tie must give one of the two legal windows
 
-def _window_candidates(st, keep, centre):
-  """(mean of the reference-legal window, ambiguous mask, list of alternative means) per column."""
-  g = st.to(torch.float64)
-  c = centre.to(torch.float64)
-  n, d = g.shape
-  srt = g.sort(dim=0).values
-  win, amb = O.closest_window(st, keep, centre)
-  # alternatives: every contiguous window of `keep` sorted values (the topk result is always one of them
-  # when deviations tie only at the window edges)
-  csum = torch.cat([torch.zeros(1, d, dtype=torch.float64), srt.cumsum(dim=0)])
-  alts = [(csum[s + keep] - csum[s]) / keep for s in range(n - keep + 1)]
-  return win, amb, alts
-
-
 @pytest.mark.parametrize("name", CASES)
 def test_closest_rules_without_exemptions(bm, name):
   g = Golden(name)
@@ -249,24 +236,9 @@ def test_closest_rules_full_size(bm):
   for rule in ("meamed", "phocas"):
     got = bm.gars.__dict__[rule](rows, f)
     centre = srt[(n - 1) // 2] if rule == "meamed" else srt[f:n - f].mean(dim=0)
-    dev = (srt - centre).abs()
-    # window start = number of leading values farther than their mirror (trmean.py:45-50 keeps the nearest)
-    lo = torch.zeros(d, dtype=torch.long, device=DEV)
-    hi = torch.full((d,), n - 1, dtype=torch.long, device=DEV)
-    cols = torch.arange(d, device=DEV)
-    for _ in range(n - keep):
-      drop_lo = dev[lo, cols] > dev[hi, cols]
-      lo = torch.where(drop_lo, lo + 1, lo)
-      hi = torch.where(drop_lo, hi, hi - 1)
-    total = torch.zeros(d, dtype=torch.float64, device=DEV)
-    for k in range(keep):
-      total += srt[lo + k, cols]
-    want = total / keep
     # near ties at the window edge: our centre may differ from torch's in the last bit (phocas), which
     # legitimately flips the choice between two values that are equally far within rounding
-    eps = 1e-6 * float(srt.abs().max())
-    tie = ((dev[(lo - 1).clamp(min=0), cols] - dev[hi, cols]).abs() <= eps) & (lo > 0) | \
-          ((dev[(hi + 1).clamp(max=n - 1), cols] - dev[lo, cols]).abs() <= eps) & (hi < n - 1)
+    want, tie = sorted_window(srt, keep, centre, 1e-6 * float(srt.abs().max()))
     bad = ((got.double() - want).abs() > 2e-6 * float(srt.abs().max())) & ~tie
     assert int(bad.sum()) == 0, (rule, int(bad.sum()))
     assert int(tie.sum()) <= d // 1000, (rule, "tie columns", int(tie.sum()))
