@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <utility>
 #include "../../include/bm_gar.h"
+#include "launch_plan.h"
 
 namespace bm {
 
@@ -13,6 +14,11 @@ namespace bm {
 // trmean.py:79) — the n x d copy is never made.
 struct RowTable {
   const float* p[BM_MAX_ROWS];
+  RowTable advanced(int64_t by) const {
+    RowTable t = *this;
+    advance(t.p, by);
+    return t;
+  }
 };
 
 static inline int hip_code(hipError_t e) { return e == hipSuccess ? 0 : -(int)e; }
@@ -193,18 +199,6 @@ __device__ __forceinline__ void store_result_policy(float* p, const float (&src)
 // Grid cap of the plain column kernels (grid-stride above it).
 constexpr int kColMaxBlocks = 256 * 64;
 
-// Columns per launch such that every byte offset fits 32 bits (saddr addressing).
-constexpr int64_t kMaxColsPerLaunch = (int64_t)1 << 29;
-
-// Largest vector width (4, 2 or 1 floats) every pointer of the table and `extra` allow.
-static inline int common_vec_width(const void* const* ptrs, int n, const void* extra) {
-  uintptr_t bits = reinterpret_cast<uintptr_t>(extra);
-  for (int i = 0; i < n; ++i) bits |= reinterpret_cast<uintptr_t>(ptrs[i]);
-  if ((bits & 15u) == 0) return 4;
-  if ((bits & 7u) == 0) return 2;
-  return 1;
-}
-
 // Dynamic LDS beyond what a launch gets without asking: ONE rule for every kernel of the library.  A launch whose
 // dynamic + static LDS exceeds 48 KB opts in through hipFuncAttributeMaxDynamicSharedMemorySize (gfx950 has 160 KB per
 // workgroup; 48 KB is the most conservative default of the parts HIP runs on, so nothing here depends on a roomier
@@ -212,15 +206,6 @@ static inline int common_vec_width(const void* const* ptrs, int n, const void* e
 static inline int lds_opt_in(const void* kernel, size_t dynamic_bytes, size_t static_bytes) {
   if (dynamic_bytes + static_bytes <= 48u * 1024u) return 0;
   return hip_code(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dynamic_bytes));
-}
-
-// Grid size for a streaming kernel: enough workgroups to fill 256 CUs several times over,
-// capped so that the grid-stride loop amortises launch/tail effects.
-static inline int stream_grid(int64_t work_items, int block, int max_blocks) {
-  int64_t g = (work_items + block - 1) / block;
-  if (g < 1) g = 1;
-  if (g > max_blocks) g = max_blocks;
-  return (int)g;
 }
 
 // Compute units of the current device (the burst forms launch one workgroup per CU).

@@ -269,34 +269,16 @@ static int launch_bulyan_eval(const float* const* honests, int h, const int32_t*
   constexpr int kMaxVec = (MMAX <= 20) ? 4 : (MMAX <= 44 ? 2 : 1);
   RowTable tab{};
   for (int i = 0; i < N; ++i) tab.p[i] = i < h ? honests[i] : avg;
-  const void* more[2] = {avg, dir};
-  int vec = common_vec_width(reinterpret_cast<const void* const*>(honests), h, nullptr);
-  const int vec2 = common_vec_width(more, 2, nullptr);
-  if (vec2 < vec) vec = vec2;
-  if (vec > kMaxVec) vec = kMaxVec;
-  const Pass2Candidate cd{avg, dir, t_dev, t, h};
+  const int vec = Alignment().of(honests, h).of(avg).of(dir).vec();
   int nparts = 0;
-  int64_t body = 0;
-  if (vec >= 2 && d / vec > 0) {
-    const int64_t nvec = d / vec;
-    const int grid = stream_grid(nvec, kBulBlock, kEvalMaxBlocks);
-    auto kern = vec == 4 ? bulyan_pass2_eval_kernel<N, F, (kMaxVec >= 4 ? 4 : 2)> : bulyan_pass2_eval_kernel<N, F, (kMaxVec >= 2 ? 2 : 1)>;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBulBlock), 0, s, tab, order, nvec, tuning().bulyan_short, cd, partial);
+  const int rc = for_body_and_tail<kMaxVec>(Tail::kOwnLaunch, vec, d, kBulBlock, kEvalCaps, [&](auto width, const Span& sp) {
+    const Pass2Candidate cd{advanced(avg, sp.first), advanced(dir, sp.first), t_dev, t, h};
+    hipLaunchKernelGGL((bulyan_pass2_eval_kernel<N, F, decltype(width)::value>), dim3(sp.grid), dim3(kBulBlock), 0, s,
+                       tab.advanced(sp.first), order, sp.count, tuning().bulyan_short, cd, partial + sp.part);
     BM_LAUNCH_CHECK();
-    nparts = grid;
-    body = nvec * vec;
-  }
-  if (body < d) {
-    RowTable tail{};
-    for (int i = 0; i < N; ++i) tail.p[i] = (i < h ? honests[i] : avg) + body;
-    const Pass2Candidate ct{avg + body, dir + body, t_dev, t, h};
-    const int64_t rest = d - body;
-    const int grid = (body == 0) ? stream_grid(rest, kBulBlock, kEvalMaxBlocks) : 1;
-    hipLaunchKernelGGL((bulyan_pass2_eval_kernel<N, F, 1>), dim3(grid), dim3(kBulBlock), 0, s, tail, order, rest,
-                       tuning().bulyan_short, ct, partial + nparts);
-    BM_LAUNCH_CHECK();
-    nparts += grid;
-  }
+    return 0;
+  }, &nparts);
+  if (rc != 0) return rc;
   hipLaunchKernelGGL(eval_finish_kernel<kEvalFinishThreads>, dim3(1), dim3(kEvalFinishThreads), 0, s, partial, nparts, out);
   BM_LAUNCH_CHECK();
   return 0;
@@ -357,32 +339,18 @@ static int launch_bulyan_fast(const float* const* rows_host, const int32_t* orde
                               float* out_all, hipStream_t s) {
   constexpr int MMAX = N - F - 2;
   constexpr int kMaxVec = (MMAX <= 20) ? 4 : (MMAX <= 44 ? 2 : 1);
-  int vec = common_vec_width(reinterpret_cast<const void* const*>(rows_host), N, out_all);
-  if (vec > kMaxVec) vec = kMaxVec;
-  // pieces of at most 2^29 columns so that byte offsets fit 32 bits inside the kernel
-  for (int64_t lo = 0; lo < d_all; lo += kMaxColsPerLaunch) {
-    const int64_t d = (d_all - lo < kMaxColsPerLaunch) ? (d_all - lo) : kMaxColsPerLaunch;
-    RowTable tab{};
-    for (int i = 0; i < N; ++i) tab.p[i] = rows_host[i] + lo;
-    float* out = out_all + lo;
-    if (vec == 4 && kMaxVec >= 4 && d / 4 > 0) {
-      const int64_t nvec = d / 4;
-      hipLaunchKernelGGL((bulyan_pass2_kernel<N, F, (kMaxVec >= 4 ? 4 : 1)>),
-                         dim3(stream_grid(nvec, kBulBlock, kColMaxBlocks)), dim3(kBulBlock), 0,
-                         s, tab, order, nvec, 1, out, tuning().bulyan_short, (int)(d - nvec * 4));
-    } else if (vec >= 2 && kMaxVec >= 2 && d / 2 > 0) {
-      const int64_t nvec = d / 2;
-      hipLaunchKernelGGL((bulyan_pass2_kernel<N, F, (kMaxVec >= 2 ? 2 : 1)>),
-                         dim3(stream_grid(nvec, kBulBlock, kColMaxBlocks)), dim3(kBulBlock), 0,
-                         s, tab, order, nvec, 1, out, tuning().bulyan_short, (int)(d - nvec * 2));
-    } else {
-      hipLaunchKernelGGL((bulyan_pass2_kernel<N, F, 1>),
-                         dim3(stream_grid(d, kBulBlock, kColMaxBlocks)), dim3(kBulBlock), 0,
-                         s, tab, order, d, 1, out, tuning().bulyan_short, 0);
-    }
-    BM_LAUNCH_CHECK();
-  }
-  return 0;
+  const int vec = Alignment().of(rows_host, N).of(out_all).vec();
+  RowTable tab{};
+  for (int i = 0; i < N; ++i) tab.p[i] = rows_host[i];
+  // pieces: byte offsets fit 32 bits inside the kernel
+  return for_pieces(d_all, [&](int64_t lo, int64_t d) {
+    return for_body_and_tail<kMaxVec>(Tail::kRidesNarrowed, vec, d, kBulBlock, caps_of(kColMaxBlocks), [&](auto width, const Span& sp) {
+      hipLaunchKernelGGL((bulyan_pass2_kernel<N, F, decltype(width)::value>), dim3(sp.grid), dim3(kBulBlock), 0, s,
+                         tab.advanced(lo), order, sp.count, 1, out_all + lo, tuning().bulyan_short, sp.tail);
+      BM_LAUNCH_CHECK();
+      return 0;
+    });
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -458,38 +426,26 @@ __global__ __launch_bounds__(64 * kAkselFinWaves) void aksel_finish_kernel(const
 }
 
 constexpr int kAkselMaxBlocks = 1024;
+constexpr Caps kAkselCaps{kAkselMaxBlocks - 1, kAkselMaxBlocks};  // BM_MAX_ROWS partials per workgroup
 
 template <int N>
 static int launch_aksel_n(const float* const* rows_host, int64_t d, float* median_out,
                           double* sq_out, double* partial, hipStream_t s) {
   RowTable tab{};
   for (int i = 0; i < N; ++i) tab.p[i] = rows_host[i];
-  int vec = common_vec_width(reinterpret_cast<const void* const*>(rows_host), N, median_out);
+  int vec = Alignment().of(rows_host, N).of(median_out).vec();
   constexpr int kMaxVec = (N <= 52) ? 2 : 1;
   if (vec > kMaxVec) vec = kMaxVec;
   if (vec == 2 && N > 28 && tuning().col_wide == 0) vec = 1;  // (BM_COL_WIDE: 8 against 4 bytes per lane beyond 28 rows, A/B)
   int nparts = 0;
-  int64_t body = 0;
-  if (vec == 2 && kMaxVec >= 2 && d / 2 > 0) {
-    const int64_t nvec = d / 2;
-    const int grid = stream_grid(nvec, kColBlock, kAkselMaxBlocks - 1);
-    hipLaunchKernelGGL((aksel_pass1_kernel<N, (kMaxVec >= 2 ? 2 : 1)>), dim3(grid), dim3(kColBlock), 0, s,
-                       tab, nvec, median_out, partial);
+  const int rc = for_body_and_tail<kMaxVec>(Tail::kOwnLaunch, vec, d, kColBlock, kAkselCaps, [&](auto width, const Span& sp) {
+    hipLaunchKernelGGL((aksel_pass1_kernel<N, decltype(width)::value>), dim3(sp.grid), dim3(kColBlock), 0, s,
+                       tab.advanced(sp.first), sp.count, advanced(median_out, sp.first),
+                       partial + (int64_t)sp.part * BM_MAX_ROWS);
     BM_LAUNCH_CHECK();
-    nparts = grid;
-    body = nvec * 2;
-  }
-  if (body < d) {
-    RowTable tail{};
-    for (int i = 0; i < N; ++i) tail.p[i] = rows_host[i] + body;
-    const int64_t rest = d - body;
-    const int grid = (body == 0) ? stream_grid(rest, kColBlock, kAkselMaxBlocks) : 1;
-    hipLaunchKernelGGL((aksel_pass1_kernel<N, 1>), dim3(grid), dim3(kColBlock), 0, s, tail, rest,
-                       median_out ? median_out + body : nullptr,
-                       partial + (int64_t)nparts * BM_MAX_ROWS);
-    BM_LAUNCH_CHECK();
-    nparts += grid;
-  }
+    return 0;
+  }, &nparts);
+  if (rc != 0) return rc;
   hipLaunchKernelGGL(aksel_finish_kernel, dim3(1), dim3(64 * kAkselFinWaves), 0, s, partial, nparts, N, sq_out);
   BM_LAUNCH_CHECK();
   return 0;
@@ -584,6 +540,10 @@ extern "C" int bm_aksel_pass1(const float* const* rows, int n, int64_t d, float*
 }
 
 namespace bm {
+// each next to the caps its launch site passes
+int64_t stats_workspace_bytes();  // reduce.hip
+int64_t dot_workspace_bytes();
+int64_t step_workspace_bytes();   // step.hip
 int64_t study_workspace_bytes();  // study.hip
 }
 
@@ -594,13 +554,13 @@ extern "C" int64_t bm_workspace_bytes(int kind, int n, int64_t d) {
     case BM_WS_PAIRWISE:
       return pairwise_workspace_bytes(n, d);
     case BM_WS_AKSEL:
-      return (int64_t)kAkselMaxBlocks * BM_MAX_ROWS * (int64_t)sizeof(double);
+      return (int64_t)kAkselCaps.sets() * BM_MAX_ROWS * (int64_t)sizeof(double);
     case BM_WS_STATS:
-      return (int64_t)2048 * 3 * (int64_t)sizeof(double);
+      return stats_workspace_bytes();
     case BM_WS_DOT:
-      return (int64_t)1025 * 42 * (int64_t)sizeof(double);
+      return dot_workspace_bytes();
     case BM_WS_STEP:
-      return (int64_t)16385 * 6 * (int64_t)sizeof(double);  // kStepMaxBlocks + 1 sets of 6 partials (step.hip)
+      return step_workspace_bytes();
     case BM_WS_STUDY:
       return study_workspace_bytes();
     default:

@@ -275,6 +275,7 @@ __global__ __launch_bounds__(kBurstThreads) void colwise_burst_kernel(RowTable r
 // workgroups per launch, and the finish kernel adds the partials in a fixed order.
 // ---------------------------------------------------------------------------------------------------
 constexpr int kEvalMaxBlocks = 2048;
+constexpr Caps kEvalCaps = caps_of(kEvalMaxBlocks);
 
 // out[0] = sum of the partials in a fixed order (1024 lanes: lane l adds l, l + 1024, ..., then the fixed tree of
 // block_reduce_sum): the search waits for this number before it can propose the next candidate, so the 64-deep

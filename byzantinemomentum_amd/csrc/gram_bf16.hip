@@ -584,7 +584,7 @@ int gram3_partials(const float* const* rows, int n, int64_t d, int64_t d_total, 
                    int* blocks_out, hipStream_t s) {
   RowTable tab{};
   for (int i = 0; i < n; ++i) tab.p[i] = rows[i];
-  const bool aligned = common_vec_width(reinterpret_cast<const void* const*>(rows), n, nullptr) == 4;
+  const bool aligned = Alignment().of(rows, n).vec() == 4;
   const int K = (n + 3) / 4;
   // Planes: the exact three-way split below 2^20 coordinates; above, two planes (x ~ h + m, 16 significant
   // bits, the remainder rounded with the coordinate dither of split2_dithered: what is dropped has zero mean and

@@ -488,7 +488,7 @@ static int pairwise_direct(const float* const* rows, int n, int64_t d, double* s
   gw.width = (int)min_width;
   const int blocks = pair_grid_blocks(gw, d);
   const bool aligned =
-      common_vec_width(reinterpret_cast<const void* const*>(rows), n, nullptr) == 4;
+      Alignment().of(rows, n).vec() == 4;
   auto kern = aligned ? pairwise_partial_kernel<true> : pairwise_partial_kernel<false>;
   // (static: the wave sums of the in-kernel reduction, 4 KB)
   if (const int rc = lds_opt_in(reinterpret_cast<const void*>(kern), lds_bytes, kRedWaves * 64 * sizeof(double))) return rc;

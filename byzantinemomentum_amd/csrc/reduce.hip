@@ -14,6 +14,8 @@ namespace bm {
 
 constexpr int kRedBlock = 256;
 constexpr int kMaxPartialBlocks = 2048;
+constexpr Caps kStatsCaps{kMaxPartialBlocks - 1, kMaxPartialBlocks};  // bm_stack_stats: 3 partials per workgroup
+constexpr int kMeanMaxBlocks = 256 * 32;
 
 // ---------------------------------------------------------------------------
 // selected_mean: out = (((0 + R[idx0]) + R[idx1]) + ... ) / m, sequential fp32.
@@ -126,9 +128,9 @@ __global__ __launch_bounds__(kMeanBurstThreads) void selected_mean_burst_kernel(
 }
 
 template <int VEC>
-static int launch_selected_mean(const RowTable& tab, const int32_t* idx, int m, int64_t nvec,
-                                float* out, hipStream_t s, int tail = 0) {
-  if (nvec <= 0) return 0;
+static int launch_selected_mean(const RowTable& tab, const int32_t* idx, int m, const Span& sp, float* out,
+                                hipStream_t s) {
+  const int64_t nvec = sp.count;
   if constexpr (VEC == 4) {
     const int cus = compute_units();
     // measured (profiles/r02_i_selected_mean_burst.txt): m = 37 at 11.2 M 306.7 -> 284.4 us, m = 18 at 36.5 M
@@ -136,14 +138,13 @@ static int launch_selected_mean(const RowTable& tab, const int32_t* idx, int m, 
     if (tuning().mean_burst > 0 && m >= 12 && nvec < ((int64_t)1 << 30) &&
         nvec / ((int64_t)cus * kMeanBurstThreads) >= tuning().mean_burst) {
       hipLaunchKernelGGL(selected_mean_burst_kernel, dim3(cus), dim3(kMeanBurstThreads), 0, s, tab, idx, m, nvec,
-                         (float)m, out, tail);
+                         (float)m, out, sp.tail);
       BM_LAUNCH_CHECK();
       return 0;
     }
   }
-  const int grid = stream_grid(nvec, kRedBlock, 256 * 32);
-  hipLaunchKernelGGL(selected_mean_kernel<VEC>, dim3(grid), dim3(kRedBlock), 0, s, tab, idx, m, nvec,
-                     (float)m, 1, out, tail);
+  hipLaunchKernelGGL(selected_mean_kernel<VEC>, dim3(sp.grid), dim3(kRedBlock), 0, s, tab, idx, m, nvec,
+                     (float)m, 1, out, sp.tail);
   BM_LAUNCH_CHECK();
   return 0;
 }
@@ -288,9 +289,17 @@ constexpr int kMaxCore = 4;
 constexpr int kMaxExtra = 32;
 constexpr int kDotSlots = kMaxCore * (kMaxCore + 1) / 2 + kMaxExtra;  // 42
 
+constexpr Caps kDotCaps = caps_of(1024);
+
 struct DotTable {
   const float* core[kMaxCore];
   const float* extra[kMaxExtra];
+  DotTable advanced(int64_t by) const {
+    DotTable t = *this;
+    advance(t.core, by);
+    advance(t.extra, by);
+    return t;
+  }
 };
 
 template <int VEC>
@@ -363,7 +372,8 @@ __global__ __launch_bounds__(64) void dot_finish_kernel(const double* __restrict
 // (blockIdx.y = row).  Behind cge.py:28-38 (`gradient.norm().item()` per gradient) and the clipping of
 // attack.py:776-779,791-794; round 2 took the norms from 4 x 4 Gram blocks (bm_multi_dot, ceil(k/4) launches).
 // ---------------------------------------------------------------------------
-constexpr int kNormBlocks = 128;  // workgroups per row: k * 128 * 8 bytes of partials fit the BM_WS_DOT workspace
+constexpr int kNormBlocks = 128;  // workgroups per row; body and tail partials of every row share the BM_WS_DOT workspace
+static_assert(2 * BM_MAX_ROWS * kNormBlocks <= kDotCaps.sets() * kDotSlots, "bm_row_sqnorms: partials exceed BM_WS_DOT");
 template <int VEC>
 __global__ __launch_bounds__(kRedBlock) void row_sqnorms_kernel(RowTable rows, int64_t nvec, double* __restrict__ partial) {
   __shared__ double red[kRedBlock / 64];
@@ -419,6 +429,12 @@ __global__ __launch_bounds__(64) void row_sqnorms_finish_kernel(const double* __
 struct AxpbyTable {
   float* y[BM_MAX_ROWS];
   const float* x[BM_MAX_ROWS];
+  AxpbyTable advanced(int64_t by) const {
+    AxpbyTable t = *this;
+    advance(t.y, by);
+    advance(t.x, by);
+    return t;
+  }
 };
 
 // (An unrolled variant with 4 vectors in flight per lane and non-temporal y accesses was measured
@@ -472,6 +488,9 @@ __global__ __launch_bounds__(64) void stable_argsort_kernel(const double* __rest
   }
 }
 
+int64_t stats_workspace_bytes() { return (int64_t)kStatsCaps.sets() * 3 * (int64_t)sizeof(double); }
+int64_t dot_workspace_bytes() { return (int64_t)kDotCaps.sets() * kDotSlots * (int64_t)sizeof(double); }
+
 }  // namespace bm
 
 extern "C" int bm_selected_mean(const float* const* rows, int n, const int32_t* idx, int m,
@@ -484,25 +503,11 @@ extern "C" int bm_selected_mean(const float* const* rows, int n, const int32_t* 
   hipStream_t s = static_cast<hipStream_t>(stream);
   RowTable tab{};
   for (int i = 0; i < n; ++i) tab.p[i] = rows[i];
-  const int vec = common_vec_width(reinterpret_cast<const void* const*>(rows), n, out);
-  int64_t body = 0;
-  int rc = 0;
-  // (the d % VEC trailing columns ride in the last workgroup of the body's launch; a launch of their own only when
-  //  there is no body)
-  if (vec == 4 && d >= 4) {
-    body = d;
-    rc = launch_selected_mean<4>(tab, idx, m, d / 4, out, s, (int)(d % 4));
-  } else if (vec >= 2 && d >= 2) {
-    body = d;
-    rc = launch_selected_mean<2>(tab, idx, m, d / 2, out, s, (int)(d % 2));
-  }
-  if (rc != 0) return rc;
-  if (body < d) {
-    RowTable tail{};
-    for (int i = 0; i < n; ++i) tail.p[i] = rows[i] + body;
-    rc = launch_selected_mean<1>(tail, idx, m, d - body, out + body, s);
-  }
-  return rc;
+  const int vec = Alignment().of(rows, n).of(out).vec();
+  // (the d % VEC trailing columns ride in the last workgroup of the body's launch: no launch of their own)
+  return for_body_and_tail<4>(Tail::kRidesNarrowed, vec, d, kRedBlock, caps_of(kMeanMaxBlocks), [&](auto width, const Span& sp) {
+    return launch_selected_mean<decltype(width)::value>(tab, idx, m, sp, out, s);
+  });
 }
 
 extern "C" int bm_stack_stats(const float* const* rows, int k, int64_t d, float* avg_out,
@@ -518,34 +523,14 @@ extern "C" int bm_stack_stats(const float* const* rows, int k, int64_t d, float*
   RowTable tab{};
   for (int i = 0; i < k; ++i) tab.p[i] = rows[i];
   double* partial = static_cast<double*>(ws);
-  int vec = common_vec_width(reinterpret_cast<const void* const*>(rows), k, avg_out);
-  if ((reinterpret_cast<uintptr_t>(scaled_out) & 15u) != 0) vec = (reinterpret_cast<uintptr_t>(scaled_out) & 7u) ? 1 : (vec > 2 ? 2 : vec);
-  int64_t body = 0;
+  const int vec = Alignment().of(rows, k).of(avg_out).of(scaled_out).vec();
   int nparts = 0;
-  int rc = 0;
-  if (vec >= 2) {
-    const int64_t nvec = d / vec;
-    if (nvec > 0) {
-      const int grid = stream_grid(nvec, kRedBlock, kMaxPartialBlocks - 1);
-      rc = (vec == 4)
-               ? dispatch_stack_stats<4>(tab, k, nvec, avg_out, scaled_out, scale, attack_kind, partial, grid, s)
-               : dispatch_stack_stats<2>(tab, k, nvec, avg_out, scaled_out, scale, attack_kind, partial, grid, s);
-      if (rc != 0) return rc;
-      nparts = grid;
-      body = nvec * vec;
-    }
-  }
-  if (body < d) {
-    RowTable tail{};
-    for (int i = 0; i < k; ++i) tail.p[i] = rows[i] + body;
-    const int64_t rest = d - body;
-    const int grid = (body == 0) ? stream_grid(rest, kRedBlock, kMaxPartialBlocks) : 1;
-    rc = dispatch_stack_stats<1>(tail, k, rest, avg_out ? avg_out + body : nullptr,
-                                 scaled_out ? scaled_out + body : nullptr, scale, attack_kind,
-                                 partial + (int64_t)nparts * 3, grid, s);
-    if (rc != 0) return rc;
-    nparts += grid;
-  }
+  const int rc = for_body_and_tail<4>(Tail::kOwnLaunch, vec, d, kRedBlock, kStatsCaps, [&](auto width, const Span& sp) {
+    return dispatch_stack_stats<decltype(width)::value>(tab.advanced(sp.first), k, sp.count, advanced(avg_out, sp.first),
+                                                        advanced(scaled_out, sp.first), scale, attack_kind,
+                                                        partial + (int64_t)sp.part * 3, sp.grid, s);
+  }, &nparts);
+  if (rc != 0) return rc;
   hipLaunchKernelGGL(stats_finish_kernel, dim3(1), dim3(64), 0, s, partial, nparts, out3);
   BM_LAUNCH_CHECK();
   return 0;
@@ -559,43 +544,18 @@ extern "C" int bm_multi_dot(const float* const* core, int nc, const float* const
     return BM_EINVAL;
   hipStream_t s = static_cast<hipStream_t>(stream);
   DotTable tab{};
-  uintptr_t bits = 0;
-  for (int i = 0; i < nc; ++i) {
-    tab.core[i] = core[i];
-    bits |= reinterpret_cast<uintptr_t>(core[i]);
-  }
-  for (int i = 0; i < ne; ++i) {
-    tab.extra[i] = extra[i];
-    bits |= reinterpret_cast<uintptr_t>(extra[i]);
-  }
+  for (int i = 0; i < nc; ++i) tab.core[i] = core[i];
+  for (int i = 0; i < ne; ++i) tab.extra[i] = extra[i];
   double* partial = static_cast<double*>(ws);
-  const int vec = (bits & 15u) == 0 ? 4 : ((bits & 7u) == 0 ? 2 : 1);
+  const int vec = Alignment().of(core, nc).of(extra, ne).vec();
   int nparts = 0;
-  int64_t body = 0;
-  if (vec >= 2 && d / vec > 0) {
-    const int64_t nvec = d / vec;
-    const int grid = stream_grid(nvec, kRedBlock, 1024);
-    if (vec == 4)
-      hipLaunchKernelGGL(multi_dot_kernel<4>, dim3(grid), dim3(kRedBlock), 0, s, tab, nc, ne, nvec,
-                         partial);
-    else
-      hipLaunchKernelGGL(multi_dot_kernel<2>, dim3(grid), dim3(kRedBlock), 0, s, tab, nc, ne, nvec,
-                         partial);
+  const int rc = for_body_and_tail<4>(Tail::kOwnLaunch, vec, d, kRedBlock, kDotCaps, [&](auto width, const Span& sp) {
+    hipLaunchKernelGGL(multi_dot_kernel<decltype(width)::value>, dim3(sp.grid), dim3(kRedBlock), 0, s,
+                       tab.advanced(sp.first), nc, ne, sp.count, partial + (int64_t)sp.part * kDotSlots);
     BM_LAUNCH_CHECK();
-    nparts = grid;
-    body = nvec * vec;
-  }
-  if (body < d) {
-    DotTable tail = tab;
-    for (int i = 0; i < nc; ++i) tail.core[i] += body;
-    for (int i = 0; i < ne; ++i) tail.extra[i] += body;
-    const int64_t rest = d - body;
-    const int grid = (body == 0) ? stream_grid(rest, kRedBlock, 1024) : 1;
-    hipLaunchKernelGGL(multi_dot_kernel<1>, dim3(grid), dim3(kRedBlock), 0, s, tail, nc, ne, rest,
-                       partial + (int64_t)nparts * kDotSlots);
-    BM_LAUNCH_CHECK();
-    nparts += grid;
-  }
+    return 0;
+  }, &nparts);
+  if (rc != 0) return rc;
   hipLaunchKernelGGL(dot_finish_kernel, dim3(kDotSlots), dim3(64), 0, s, partial, nparts, nc, ne, out);
   BM_LAUNCH_CHECK();
   return 0;
@@ -608,36 +568,17 @@ extern "C" int bm_multi_axpby(float* const* y, const float* const* x, int k, int
   if (d == 0) return 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
   AxpbyTable tab{};
-  uintptr_t bits = 0;
   for (int i = 0; i < k; ++i) {
     tab.y[i] = y[i];
     tab.x[i] = x[i];
-    bits |= reinterpret_cast<uintptr_t>(y[i]) | reinterpret_cast<uintptr_t>(x[i]);
   }
-  const int vec = (bits & 15u) == 0 ? 4 : ((bits & 7u) == 0 ? 2 : 1);
-  int64_t body = 0;
-  if (vec >= 2 && d / vec > 0) {
-    const int64_t nvec = d / vec;
-    const int grid = stream_grid(nvec, kRedBlock, 2048);
-    if (vec == 4)
-      hipLaunchKernelGGL(multi_axpby_kernel<4>, dim3(grid, k), dim3(kRedBlock), 0, s, tab, nvec, a, b);
-    else
-      hipLaunchKernelGGL(multi_axpby_kernel<2>, dim3(grid, k), dim3(kRedBlock), 0, s, tab, nvec, a, b);
+  const int vec = Alignment().of(y, k).of(x, k).vec();
+  return for_body_and_tail<4>(Tail::kOwnLaunch, vec, d, kRedBlock, caps_of(2048), [&](auto width, const Span& sp) {
+    hipLaunchKernelGGL(multi_axpby_kernel<decltype(width)::value>, dim3(sp.grid, k), dim3(kRedBlock), 0, s,
+                       tab.advanced(sp.first), sp.count, a, b);
     BM_LAUNCH_CHECK();
-    body = nvec * vec;
-  }
-  if (body < d) {
-    AxpbyTable tail = tab;
-    for (int i = 0; i < k; ++i) {
-      tail.y[i] += body;
-      tail.x[i] += body;
-    }
-    const int64_t rest = d - body;
-    const int grid = stream_grid(rest, kRedBlock, 2048);
-    hipLaunchKernelGGL(multi_axpby_kernel<1>, dim3(grid, k), dim3(kRedBlock), 0, s, tail, rest, a, b);
-    BM_LAUNCH_CHECK();
-  }
-  return 0;
+    return 0;
+  });
 }
 
 extern "C" int bm_stable_argsort(const double* keys, int n, int32_t* order_out, void* stream) {
@@ -655,29 +596,20 @@ extern "C" int bm_row_sqnorms(const float* const* rows, int k, int64_t d, double
   hipStream_t s = static_cast<hipStream_t>(stream);
   RowTable tab{};
   for (int i = 0; i < k; ++i) tab.p[i] = rows[i];
-  const int vec = common_vec_width(reinterpret_cast<const void* const*>(rows), k, nullptr);
+  const int vec = Alignment().of(rows, k).vec();
   double* body_part = static_cast<double*>(ws);
   double* tail_part = body_part + (int64_t)BM_MAX_ROWS * kNormBlocks;
   int nbody = 0, ntail = 0;
-  int64_t body = 0;
-  if (vec >= 2 && d / vec > 0) {
-    const int64_t nvec = d / vec;
-    nbody = stream_grid(nvec, kRedBlock, kNormBlocks);
-    if (vec == 4)
-      hipLaunchKernelGGL(row_sqnorms_kernel<4>, dim3(nbody, k), dim3(kRedBlock), 0, s, tab, nvec, body_part);
-    else
-      hipLaunchKernelGGL(row_sqnorms_kernel<2>, dim3(nbody, k), dim3(kRedBlock), 0, s, tab, nvec, body_part);
+  // (partials are row-major per launch, so body and tail keep an area each: under kOwnLaunch the VEC = 1 launch is the tail)
+  const int rc = for_body_and_tail<4>(Tail::kOwnLaunch, vec, d, kRedBlock, caps_of(kNormBlocks), [&](auto width, const Span& sp) {
+    constexpr int VEC = decltype(width)::value;
+    (VEC == 1 ? ntail : nbody) = sp.grid;
+    hipLaunchKernelGGL(row_sqnorms_kernel<VEC>, dim3(sp.grid, k), dim3(kRedBlock), 0, s, tab.advanced(sp.first), sp.count,
+                       VEC == 1 ? tail_part : body_part);
     BM_LAUNCH_CHECK();
-    body = nvec * vec;
-  }
-  if (body < d) {
-    RowTable tail{};
-    for (int i = 0; i < k; ++i) tail.p[i] = rows[i] + body;
-    const int64_t rest = d - body;
-    ntail = (body == 0) ? stream_grid(rest, kRedBlock, kNormBlocks) : 1;
-    hipLaunchKernelGGL(row_sqnorms_kernel<1>, dim3(ntail, k), dim3(kRedBlock), 0, s, tail, rest, tail_part);
-    BM_LAUNCH_CHECK();
-  }
+    return 0;
+  });
+  if (rc != 0) return rc;
   // d == 0: no partial at all, the finish kernel writes zeros
   hipLaunchKernelGGL(row_sqnorms_finish_kernel, dim3(k), dim3(64), 0, s, body_part, nbody, tail_part, ntail, sq_out);
   BM_LAUNCH_CHECK();

@@ -84,32 +84,16 @@ static int launch_eval(const float* const* rows, int h, int64_t d, int f, const 
   const float inv_keep = 1.0f / (float)(keep > 0 ? keep : 1);
   RowTable tab{};
   for (int i = 0; i < h; ++i) tab.p[i] = rows[i];
-  const void* more[2] = {avg, dir};
-  int vec = common_vec_width(reinterpret_cast<const void* const*>(rows), h, nullptr);
-  const int vec2 = common_vec_width(more, 2, nullptr);
-  if (vec2 < vec) vec = vec2;
-  if (vec > kMaxVec) vec = kMaxVec;
+  const int vec = Alignment().of(rows, h).of(avg).of(dir).vec();
   int nparts = 0;
-  int64_t body = 0;
-  if (vec >= 2 && d / vec > 0) {
-    const int64_t nvec = d / vec;
-    const int grid = stream_grid(nvec, kColBlock, kEvalMaxBlocks);
-    auto kern = vec == 4 ? colwise_eval_kernel<N, OP, (kMaxVec >= 4 ? 4 : 2)> : colwise_eval_kernel<N, OP, 2>;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kColBlock), 0, s, tab, h, avg, dir, t, t_dev, nvec, f, inv_keep, partial);
+  const int rc = for_body_and_tail<kMaxVec>(Tail::kOwnLaunch, vec, d, kColBlock, kEvalCaps, [&](auto width, const Span& sp) {
+    hipLaunchKernelGGL((colwise_eval_kernel<N, OP, decltype(width)::value>), dim3(sp.grid), dim3(kColBlock), 0, s,
+                       tab.advanced(sp.first), h, advanced(avg, sp.first), advanced(dir, sp.first), t, t_dev, sp.count, f,
+                       inv_keep, partial + sp.part);
     BM_LAUNCH_CHECK();
-    nparts = grid;
-    body = nvec * vec;
-  }
-  if (body < d) {
-    RowTable tail{};
-    for (int i = 0; i < h; ++i) tail.p[i] = rows[i] + body;
-    const int64_t rest = d - body;
-    const int grid = (body == 0) ? stream_grid(rest, kColBlock, kEvalMaxBlocks) : 1;
-    hipLaunchKernelGGL((colwise_eval_kernel<N, OP, 1>), dim3(grid), dim3(kColBlock), 0, s, tail, h, avg + body, dir + body,
-                       t, t_dev, rest, f, inv_keep, partial + nparts);
-    BM_LAUNCH_CHECK();
-    nparts += grid;
-  }
+    return 0;
+  }, &nparts);
+  if (rc != 0) return rc;
   // d == 0: no partial, the finish kernel writes zero (every rank of a sharded job reaches its all-reduce)
   hipLaunchKernelGGL(eval_finish_kernel<kEvalFinishThreads>, dim3(1), dim3(kEvalFinishThreads), 0, s, partial, nparts, out);
   BM_LAUNCH_CHECK();
@@ -214,30 +198,13 @@ static int launch_order_pair(const float* const* rows, int h, int64_t d, int il,
   constexpr int kMaxVec = (N <= 28) ? 4 : 2;
   RowTable tab{};
   for (int i = 0; i < h; ++i) tab.p[i] = rows[i];
-  const void* outs[2] = {lo, hi};
-  int vec = common_vec_width(reinterpret_cast<const void* const*>(rows), h, nullptr);
-  const int vec2 = common_vec_width(outs, 2, nullptr);
-  if (vec2 < vec) vec = vec2;
-  if (vec > kMaxVec) vec = kMaxVec;
-  int64_t body = 0;
-  if (vec >= 2 && d / vec > 0) {
-    const int64_t nvec = d / vec;
-    const int grid = stream_grid(nvec, kColBlock, kColMaxBlocks);
-    auto kern = vec == 4 ? order_pair_kernel<N, (kMaxVec >= 4 ? 4 : 2)> : order_pair_kernel<N, 2>;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kColBlock), 0, s, tab, h, il, ih, nvec, lo, hi);
+  const int vec = Alignment().of(rows, h).of(lo).of(hi).vec();
+  return for_body_and_tail<kMaxVec>(Tail::kOwnLaunch, vec, d, kColBlock, caps_of(kColMaxBlocks), [&](auto width, const Span& sp) {
+    hipLaunchKernelGGL((order_pair_kernel<N, decltype(width)::value>), dim3(sp.grid), dim3(kColBlock), 0, s,
+                       tab.advanced(sp.first), h, il, ih, sp.count, lo + sp.first, hi + sp.first);
     BM_LAUNCH_CHECK();
-    body = nvec * vec;
-  }
-  if (body < d) {
-    RowTable tail{};
-    for (int i = 0; i < h; ++i) tail.p[i] = rows[i] + body;
-    const int64_t rest = d - body;
-    const int grid = (body == 0) ? stream_grid(rest, kColBlock, kColMaxBlocks) : 1;
-    hipLaunchKernelGGL((order_pair_kernel<N, 1>), dim3(grid), dim3(kColBlock), 0, s, tail, h, il, ih, rest, lo + body,
-                       hi + body);
-    BM_LAUNCH_CHECK();
-  }
-  return 0;
+    return 0;
+  });
 }
 
 }  // namespace bm
@@ -270,34 +237,23 @@ extern "C" int bm_sqdist2(const float* a, const float* b, int64_t d, double* out
   if (out == nullptr || ws == nullptr || d < 0 || (d > 0 && (a == nullptr || b == nullptr))) return BM_EINVAL;
   hipStream_t s = static_cast<hipStream_t>(stream);
   double* partial = static_cast<double*>(ws);
-  const void* both[2] = {a, b};
-  const int vec = d > 0 ? common_vec_width(both, 2, nullptr) : 1;
+  const int vec = Alignment().of(a).of(b).vec();
   int nparts = 0;
-  int64_t body = 0;
-  if (vec >= 2 && d / vec > 0) {
-    const int64_t nvec = d / vec;
-    const int grid = stream_grid(nvec, kColBlock, kEvalMaxBlocks);
-    if (vec == 4)
-      hipLaunchKernelGGL(sqdist2_kernel<4>, dim3(grid), dim3(kColBlock), 0, s, a, b, nvec, partial);
-    else
-      hipLaunchKernelGGL(sqdist2_kernel<2>, dim3(grid), dim3(kColBlock), 0, s, a, b, nvec, partial);
+  const int rc = for_body_and_tail<4>(Tail::kOwnLaunch, vec, d, kColBlock, kEvalCaps, [&](auto width, const Span& sp) {
+    hipLaunchKernelGGL(sqdist2_kernel<decltype(width)::value>, dim3(sp.grid), dim3(kColBlock), 0, s, a + sp.first,
+                       b + sp.first, sp.count, partial + sp.part);
     BM_LAUNCH_CHECK();
-    nparts = grid;
-    body = nvec * vec;
-  }
-  if (body < d) {
-    const int64_t rest = d - body;
-    const int grid = (body == 0) ? stream_grid(rest, kColBlock, kEvalMaxBlocks) : 1;
-    hipLaunchKernelGGL(sqdist2_kernel<1>, dim3(grid), dim3(kColBlock), 0, s, a + body, b + body, rest, partial + nparts);
-    BM_LAUNCH_CHECK();
-    nparts += grid;
-  }
+    return 0;
+  }, &nparts);
+  if (rc != 0) return rc;
   // d == 0: no partial, the finish kernel writes zero (every rank of a sharded job reaches its all-reduce)
   hipLaunchKernelGGL(eval_finish_kernel<kEvalFinishThreads>, dim3(1), dim3(kEvalFinishThreads), 0, s, partial, nparts, out);
   BM_LAUNCH_CHECK();
   return 0;
 }
 
+// (twice the cap: room to spare over the kEvalCaps.sets() partials a call writes)
+static_assert(bm::kEvalCaps.sets() <= 2 * bm::kEvalMaxBlocks, "evaluate-only partials exceed their workspace");
 extern "C" int64_t bm_colwise_eval_workspace_bytes(void) { return (int64_t)(2 * bm::kEvalMaxBlocks) * (int64_t)sizeof(double); }
 
 static int colwise_eval_call(int op, const float* const* honests, int h, int copies, int64_t d, int f, const float* avg,

@@ -20,11 +20,19 @@
 namespace bm {
 
 constexpr int kStepBlock = 256;
-constexpr int kStepMaxBlocks = 16384;  // per-workgroup partials: bm_workspace_bytes(BM_WS_STEP) holds kStepMaxBlocks + 1 sets
+constexpr int kStepMaxBlocks = 16384;  // per-workgroup partials: bm_workspace_bytes(BM_WS_STEP) holds kStepMaxBlocks + 1 sets of 6
+constexpr int kStepPieceCap = 2047;    // workgroups of one launch of the first pass
+static_assert(caps_of(kStepPieceCap).sets() <= kStepMaxBlocks + 1, "first pass: partials exceed BM_WS_STEP");
 
 struct StepTable {
   const float* g[BM_MAX_ROWS];  // sampled gradients (ks)
   float* b[BM_MAX_ROWS];        // momentum buffers (h), updated in place
+  StepTable advanced(int64_t by) const {
+    StepTable t = *this;
+    advance(t.g, by);
+    advance(t.b, by);
+    return t;
+  }
 };
 
 // NaN-propagating max of |.| partials across a workgroup; result valid on thread 0
@@ -759,6 +767,13 @@ struct Fma3Table {
   float* out[BM_MAX_ROWS];
   const float* p[BM_MAX_ROWS];
   const float* q[BM_MAX_ROWS];
+  Fma3Table advanced(int64_t by) const {
+    Fma3Table t = *this;
+    advance(t.out, by);
+    advance(t.p, by);
+    advance(t.q, by);
+    return t;
+  }
 };
 
 template <int VEC>
@@ -790,6 +805,11 @@ __global__ __launch_bounds__(kStepBlock) void multi_fma3_kernel(Fma3Table tab, i
 // attack.py:776-779,791-794 once the factors are known.
 struct ScaleTable {
   float* y[BM_MAX_ROWS];
+  ScaleTable advanced(int64_t by) const {
+    ScaleTable t = *this;
+    advance(t.y, by);
+    return t;
+  }
 };
 template <int VEC>
 __global__ __launch_bounds__(kStepBlock) void multi_scale_kernel(ScaleTable tab, int64_t nvec,
@@ -911,11 +931,8 @@ __global__ __launch_bounds__(256) void tail_gram_kernel(RowTable rows /* the buf
   block[b3_tri_index(i, j, nrows)] = acc;
 }
 
-static inline int vec_of(uintptr_t bits) { return (bits & 15u) == 0 ? 4 : ((bits & 7u) == 0 ? 2 : 1); }
+int64_t step_workspace_bytes() { return (int64_t)(kStepMaxBlocks + 1) * 6 * (int64_t)sizeof(double); }
 
-}  // namespace bm
-
-namespace bm {
 // rule_op < 0: the first pass alone (bm_momentum_stats); else also defense = rule(buffers + [byz] * nb) (bm_momentum_stats_colwise)
 static int momentum_stats_impl(const float* const* sampled, int ks, float* const* buffers, int h, int64_t d, float mu,
                                float one_minus_damp, const float* clip_factors, float* sampled_avg, float* honest_avg,
@@ -931,85 +948,51 @@ static int momentum_stats_impl(const float* const* sampled, int ks, float* const
     return BM_EINVAL;
   hipStream_t s = static_cast<hipStream_t>(stream);
   StepTable tab{};
-  uintptr_t bits = reinterpret_cast<uintptr_t>(sampled_avg) | reinterpret_cast<uintptr_t>(honest_avg) |
-                   reinterpret_cast<uintptr_t>(byz_out) | reinterpret_cast<uintptr_t>(rule_op >= 0 ? defense_out : nullptr);
-  for (int i = 0; i < ks; ++i) {
-    tab.g[i] = sampled[i];
-    bits |= reinterpret_cast<uintptr_t>(sampled[i]);
-  }
-  for (int i = 0; i < h; ++i) {
-    tab.b[i] = buffers[i];
-    bits |= reinterpret_cast<uintptr_t>(buffers[i]);
-  }
+  for (int i = 0; i < ks; ++i) tab.g[i] = sampled[i];
+  for (int i = 0; i < h; ++i) tab.b[i] = buffers[i];
   // pad the tables with their last row: the streaming kernel loads whole batches unconditionally
   for (int i = ks; i < BM_MAX_ROWS; ++i) tab.g[i] = sampled[ks - 1];
   for (int i = h; i < BM_MAX_ROWS; ++i) tab.b[i] = buffers[h - 1];
+  const int vec = Alignment().of(sampled_avg).of(honest_avg).of(byz_out).of(rule_op >= 0 ? defense_out : nullptr)
+                      .of(sampled, ks).of(buffers, h).vec();
   double* partial = static_cast<double*>(ws);
-  const int vec = vec_of(bits);
-  // pieces of at most 2^29 coordinates: byte offsets fit 32 bits inside the register-resident kernel
-  const int64_t pieces = d > 0 ? (d + kMaxColsPerLaunch - 1) / kMaxColsPerLaunch : 0;
-  int cap = pieces > 1 ? (int)((kStepMaxBlocks - 1) / pieces) - 1 : 2047;
-  if (cap > 2047) cap = 2047;
+  // pieces (byte offsets fit 32 bits inside the register-resident kernel) share the workspace: each leaves at most
+  // cap + 1 partial sets, all of them at most kStepMaxBlocks + 1
+  const int64_t pieces = piece_count(d);
+  int cap = pieces > 1 ? (int)((kStepMaxBlocks - 1) / pieces) - 1 : kStepPieceCap;
+  if (cap > kStepPieceCap) cap = kStepPieceCap;
   if (cap < 1) return BM_EINVAL;  // d >= 2^42: not a gradient
+  // the rule inside the first pass where an instance exists (16-byte columns, ks = h = 20 / 14 with 5 / 11 Byzantine copies)
+  const bool fusable = rule_op >= 0 && fused_rule_instance(ks, h, nb, rule_op);
   int nparts = 0;
-  int rc = 0;
-  for (int64_t lo = 0; lo < d; lo += kMaxColsPerLaunch) {
-    const int64_t dp = (d - lo < kMaxColsPerLaunch) ? (d - lo) : kMaxColsPerLaunch;
-    StepTable piece = tab;
-    for (int i = 0; i < BM_MAX_ROWS; ++i) {
-      piece.g[i] += lo;
-      piece.b[i] += lo;
-    }
-    float* sa = sampled_avg ? sampled_avg + lo : nullptr;
-    float* ha = honest_avg ? honest_avg + lo : nullptr;
-    float* bz = byz_out ? byz_out + lo : nullptr;
-    int64_t body = 0;
-    // the rule inside the first pass where an instance exists (16-byte columns, ks = h = 20, 1..6 Byzantine copies)
-    const bool fused = rule_op >= 0 && vec == 4 && dp / 4 > 0 && fused_rule_instance(ks, h, nb, rule_op);
-    if (fused) {
-      const int64_t nvec = dp / 4;
-      int grid = stream_grid(nvec, kStepBlock, cap);
-      rc = launch_fused_rule_any(rule_op, h, nb, piece, nvec, mu, one_minus_damp, clip_factors, sa, ha, bz, scale,
-                                 attack_kind, partial + (int64_t)nparts * 6, rule_f, defense_out + lo, &grid, s);
-      if (rc != 0) return rc;
-      nparts += grid;
-      body = nvec * 4;
-    } else if (vec >= 2 && dp / vec > 0) {
-      const int64_t nvec = dp / vec;
-      int grid = stream_grid(nvec, kStepBlock, cap);
-      rc = (vec == 4) ? dispatch_momentum_stats<4>(piece, ks, h, nvec, mu, one_minus_damp, clip_factors, sa, ha, bz,
-                                                    scale, attack_kind, partial + (int64_t)nparts * 6, &grid, s)
-                      : dispatch_momentum_stats<2>(piece, ks, h, nvec, mu, one_minus_damp, clip_factors, sa, ha, bz,
-                                                    scale, attack_kind, partial + (int64_t)nparts * 6, &grid, s);
-      if (rc != 0) return rc;
-      nparts += grid;
-      body = nvec * vec;
-    }
-    if (body < dp) {
-      StepTable tail = piece;
-      for (int i = 0; i < BM_MAX_ROWS; ++i) {
-        tail.g[i] += body;
-        tail.b[i] += body;
+  const int rc = for_pieces(d, [&](int64_t lo, int64_t dp) {
+    const StepTable piece = tab.advanced(lo);
+    float* sa = advanced(sampled_avg, lo);
+    float* ha = advanced(honest_avg, lo);
+    float* bz = advanced(byz_out, lo);
+    int64_t ruled = 0;  // columns of this piece the fused kernel covered
+    const int rc = for_body_and_tail<4>(Tail::kOwnLaunch, vec, dp, kStepBlock, caps_of(cap), [&](auto width, Span& sp) {
+      constexpr int VEC = decltype(width)::value;
+      double* part = partial + (int64_t)sp.part * 6;
+      if constexpr (VEC == 4) {
+        if (fusable) {
+          ruled = sp.end;
+          return launch_fused_rule_any(rule_op, h, nb, piece, sp.count, mu, one_minus_damp, clip_factors, sa, ha, bz, scale,
+                                       attack_kind, part, rule_f, defense_out + lo, &sp.grid, s);
+        }
       }
-      const int64_t rest = dp - body;
-      int grid = (body == 0) ? stream_grid(rest, kStepBlock, cap) : 1;
-      rc = dispatch_momentum_stats<1>(tail, ks, h, rest, mu, one_minus_damp, clip_factors, sa ? sa + body : nullptr,
-                                      ha ? ha + body : nullptr, bz ? bz + body : nullptr, scale, attack_kind,
-                                      partial + (int64_t)nparts * 6, &grid, s);
-      if (rc != 0) return rc;
-      nparts += grid;
-    }
-    if (rule_op >= 0) {  // the columns of this piece the fused kernel did not cover: the rule as its own launch
-      const int64_t from = fused ? body : 0;
-      if (from < dp) {
-        const float* rows[BM_MAX_ROWS];
-        for (int i = 0; i < h; ++i) rows[i] = buffers[i] + lo + from;
-        for (int i = 0; i < nb; ++i) rows[h + i] = byz_out + lo + from;
-        rc = bm_colwise(rule_op, rows, h + nb, dp - from, rule_f, defense_out + lo + from, stream);
-        if (rc != 0) return rc;
-      }
-    }
-  }
+      return dispatch_momentum_stats<VEC>(piece.advanced(sp.first), ks, h, sp.count, mu, one_minus_damp, clip_factors,
+                                          advanced(sa, sp.first), advanced(ha, sp.first), advanced(bz, sp.first), scale,
+                                          attack_kind, part, &sp.grid, s);
+    }, &nparts);
+    if (rc != 0 || rule_op < 0 || ruled == dp) return rc;
+    // the columns of this piece the fused kernel did not cover: the rule as its own launch
+    const float* rows[BM_MAX_ROWS];
+    for (int i = 0; i < h; ++i) rows[i] = buffers[i] + lo + ruled;
+    for (int i = 0; i < nb; ++i) rows[h + i] = byz_out + lo + ruled;
+    return bm_colwise(rule_op, rows, h + nb, dp - ruled, rule_f, defense_out + lo + ruled, stream);
+  });
+  if (rc != 0) return rc;
   // d == 0: nparts == 0 and the finish kernel writes zeros — every rank of a sharded job reaches its collective
   hipLaunchKernelGGL(step_finish_kernel, dim3(1), dim3(kFinishThreads), 0, s, partial, nparts, out6);
   BM_LAUNCH_CHECK();
@@ -1057,17 +1040,13 @@ extern "C" int bm_momentum_stats_sqdist(const float* const* sampled, int ks, flo
   const float* rows[BM_MAX_ROWS];
   for (int i = 0; i < h; ++i) rows[i] = buffers[i];
   for (int i = h; i < n; ++i) rows[i] = byz_out;
-  uintptr_t bits = reinterpret_cast<uintptr_t>(sampled_avg) | reinterpret_cast<uintptr_t>(honest_avg) |
-                   reinterpret_cast<uintptr_t>(byz_out);
-  for (int i = 0; i < ks; ++i) bits |= reinterpret_cast<uintptr_t>(sampled[i]);
-  for (int i = 0; i < h; ++i) bits |= reinterpret_cast<uintptr_t>(buffers[i]);
+  const int vec = Alignment().of(sampled_avg).of(honest_avg).of(byz_out).of(sampled, ks).of(buffers, h).vec();
   const int cus = compute_units();
-  const int64_t nvec = d / 4;
   const bool shape_ok = ks == h && ((h == 20 && n_byz <= 6) || (h == 14 && n_byz == 11));  // n = 25 with f = 5 / 11, and neighbours
-  const bool fused = shape_ok && vec_of(bits) == 4 && honest_avg != nullptr &&
+  const bool fused = shape_ok && vec == 4 && honest_avg != nullptr &&
                      d <= kMaxColsPerLaunch && tuning().step_stream != 1 && tuning().pair_mode == 0 &&
                      tuning().pair_planes != 3 && tuning().step_burst > 0 &&
-                     nvec / ((int64_t)cus * kStepBurstBlock) >= tuning().step_burst;
+                     d / 4 / ((int64_t)cus * kStepBurstBlock) >= tuning().step_burst;
   if (!fused) {  // the two passes one after the other: same results as the fused kernel up to the distances' rounding
     int rc = bm_momentum_stats(sampled, ks, buffers, h, d, mu, one_minus_damp, clip_factors, sampled_avg, honest_avg,
                                byz_out, scale, attack_kind, out6, ws, stream);
@@ -1095,32 +1074,37 @@ extern "C" int bm_momentum_stats_sqdist(const float* const* sampled, int ks, flo
   }
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   if (e != hipSuccess) return hip_code(e);
-  hipLaunchKernelGGL(kern, dim3(cus), dim3(kStepBurstBlock), lds, s, tab, (uint32_t)nvec, mu, one_minus_damp,
-                     clip_factors, sampled_avg, honest_avg, byz_out, scale, attack_kind, (unsigned)tuning().pair_dither,
-                     partial, gram_partial, pairwise_arrival_counter(ws_pair), tuning().step_stagger_us * 100);
-  BM_LAUNCH_CHECK();
-  int nparts = cus, blocks = cus;
-  const int64_t body = nvec * 4;
-  if (body < d) {  // at most 3 trailing columns: the scalar form of the first pass, and their Gram as one more block
-    StepTable tail = tab;
-    for (int i = 0; i < BM_MAX_ROWS; ++i) {
-      tail.g[i] += body;
-      tail.b[i] += body;
+  int nparts = 0, blocks = 0;
+  // body: one workgroup per CU; the at most 3 trailing columns: the scalar form of the first pass, and their Gram as one more block
+  const int rc = for_body_and_tail<4>(Tail::kOwnLaunch, vec, d, kStepBlock, caps_of(kStepPieceCap), [&](auto width, Span& sp) {
+    constexpr int VEC = decltype(width)::value;
+    if constexpr (VEC == 4) {
+      sp.grid = cus;
+      hipLaunchKernelGGL(kern, dim3(cus), dim3(kStepBurstBlock), lds, s, tab, (uint32_t)sp.count, mu, one_minus_damp,
+                         clip_factors, sampled_avg, honest_avg, byz_out, scale, attack_kind, (unsigned)tuning().pair_dither,
+                         partial, gram_partial, pairwise_arrival_counter(ws_pair), tuning().step_stagger_us * 100);
+      BM_LAUNCH_CHECK();
+      blocks = cus;
+      return 0;
+    } else if constexpr (VEC == 1) {
+      if (const int rc = dispatch_momentum_stats<1>(tab.advanced(sp.first), ks, h, sp.count, mu, one_minus_damp, clip_factors,
+                                                    advanced(sampled_avg, sp.first), honest_avg + sp.first,
+                                                    byz_out + sp.first, scale, attack_kind,
+                                                    partial + (int64_t)sp.part * 6, &sp.grid, s))
+        return rc;
+      RowTable trows{};
+      for (int i = 0; i < h; ++i) trows.p[i] = buffers[i] + sp.first;
+      trows.p[h] = byz_out + sp.first;
+      hipLaunchKernelGGL(tail_gram_kernel, dim3(1), dim3(256), 0, s, trows, nc, honest_avg + sp.first, (int)sp.count,
+                         gram_partial + (int64_t)blocks * per_block);
+      BM_LAUNCH_CHECK();
+      blocks += 1;
+      return 0;
+    } else {
+      return BM_EINVAL;  // (the fused form runs on 16-byte columns only)
     }
-    int grid = 1;
-    int rc = dispatch_momentum_stats<1>(tail, ks, h, d - body, mu, one_minus_damp, clip_factors,
-                                        sampled_avg ? sampled_avg + body : nullptr, honest_avg + body, byz_out + body,
-                                        scale, attack_kind, partial + (int64_t)nparts * 6, &grid, s);
-    if (rc != 0) return rc;
-    nparts += grid;
-    RowTable trows{};
-    for (int i = 0; i < h; ++i) trows.p[i] = buffers[i] + body;
-    trows.p[h] = byz_out + body;
-    hipLaunchKernelGGL(tail_gram_kernel, dim3(1), dim3(256), 0, s, trows, nc, honest_avg + body, (int)(d - body),
-                       gram_partial + (int64_t)blocks * per_block);
-    BM_LAUNCH_CHECK();
-    blocks += 1;
-  }
+  }, &nparts);
+  if (rc != 0) return rc;
   hipLaunchKernelGGL(step_finish_kernel, dim3(1), dim3(kFinishThreads), 0, s, partial, nparts, out6);
   BM_LAUNCH_CHECK();
   return pairwise_from_gram_partials(rows, n, nc, blocks, d, sq_nxn, ws_pair, s);
@@ -1154,10 +1138,8 @@ extern "C" int bm_stack_stats_colwise(const float* const* rows, int k, int64_t d
       (d > 0 && (avg_out == nullptr || byz_out == nullptr || defense_out == nullptr)))
     return BM_EINVAL;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  uintptr_t bits = reinterpret_cast<uintptr_t>(avg_out) | reinterpret_cast<uintptr_t>(byz_out) |
-                   reinterpret_cast<uintptr_t>(defense_out);
-  for (int i = 0; i < k; ++i) bits |= reinterpret_cast<uintptr_t>(rows[i]);
-  const bool fused = fused_rule_shape(k, n_byz) && vec_of(bits) == 4 && d % 4 == 0 && d > 0 && d <= kMaxColsPerLaunch &&
+  const int vec = Alignment().of(avg_out).of(byz_out).of(defense_out).of(rows, k).vec();
+  const bool fused = fused_rule_shape(k, n_byz) && vec == 4 && d % 4 == 0 && d > 0 && d <= kMaxColsPerLaunch &&
                      tuning().step_stream != 1;
   if (fused) {
     StepTable tab{};
@@ -1166,12 +1148,17 @@ extern "C" int bm_stack_stats_colwise(const float* const* rows, int k, int64_t d
       tab.b[i] = nullptr;  // never dereferenced without momentum
     }
     double* partial = static_cast<double*>(ws);
-    const int64_t nvec = d / 4;
-    int grid = stream_grid(nvec, kStepBlock, 2047);
-    int rc = launch_fused_rule_any(rule_op, k, n_byz, tab, nvec, 0.0f, 1.0f, nullptr, nullptr, avg_out, byz_out, scale,
-                                   attack_kind, partial, rule_f, defense_out, &grid, s, true);
+    int nparts = 0;
+    // (d % 4 == 0: the body is the whole pass)
+    const int rc = for_body_and_tail<4>(Tail::kOwnLaunch, vec, d, kStepBlock, caps_of(kStepPieceCap), [&](auto width, Span& sp) {
+      if constexpr (decltype(width)::value == 4)
+        return launch_fused_rule_any(rule_op, k, n_byz, tab, sp.count, 0.0f, 1.0f, nullptr, nullptr, avg_out, byz_out, scale,
+                                     attack_kind, partial, rule_f, defense_out, &sp.grid, s, true);
+      else
+        return BM_EINVAL;
+    }, &nparts);
     if (rc != 0) return rc;
-    hipLaunchKernelGGL(step_finish_kernel, dim3(1), dim3(kFinishThreads), 0, s, partial, grid, out6);
+    hipLaunchKernelGGL(step_finish_kernel, dim3(1), dim3(kFinishThreads), 0, s, partial, nparts, out6);
     BM_LAUNCH_CHECK();
     return 0;
   }
@@ -1197,11 +1184,10 @@ extern "C" int bm_stack_stats_sqdist(const float* const* rows, int k, int64_t d,
   const float* all[BM_MAX_ROWS];
   for (int i = 0; i < k; ++i) all[i] = rows[i];
   for (int i = k; i < n; ++i) all[i] = byz_out;
-  uintptr_t bits = reinterpret_cast<uintptr_t>(avg_out) | reinterpret_cast<uintptr_t>(byz_out);
-  for (int i = 0; i < k; ++i) bits |= reinterpret_cast<uintptr_t>(rows[i]);
+  const int vec = Alignment().of(avg_out).of(byz_out).of(rows, k).vec();
   const int cus = compute_units();
   const int64_t nvec = d / 4;
-  const bool fused = nomom_shape(k, n_byz) && vec_of(bits) == 4 && d % 4 == 0 && d <= kMaxColsPerLaunch &&
+  const bool fused = nomom_shape(k, n_byz) && vec == 4 && d % 4 == 0 && d <= kMaxColsPerLaunch &&
                      tuning().step_stream != 1 && tuning().pair_mode == 0 && tuning().pair_planes != 3 &&
                      tuning().step_burst > 0 && nvec / ((int64_t)cus * kStepBurstBlock) >= tuning().step_burst;
   if (!fused) {
@@ -1244,38 +1230,18 @@ static int multi_fma3_launch(float* const* out, const float* const* p, const flo
   if (d == 0) return 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
   Fma3Table tab{};
-  uintptr_t bits = 0;
   for (int i = 0; i < k; ++i) {
     tab.out[i] = out[i];
     tab.p[i] = p[i];
     tab.q[i] = q[i];
-    bits |= reinterpret_cast<uintptr_t>(out[i]) | reinterpret_cast<uintptr_t>(p[i]) | reinterpret_cast<uintptr_t>(q[i]);
   }
-  const int vec = vec_of(bits);
-  int64_t body = 0;
-  if (vec >= 2 && d / vec > 0) {
-    const int64_t nvec = d / vec;
-    const int grid = stream_grid(nvec, kStepBlock, 2048);
-    if (vec == 4)
-      hipLaunchKernelGGL(multi_fma3_kernel<4>, dim3(grid, k), dim3(kStepBlock), 0, s, tab, nvec, a, b, p_scale, b_dev);
-    else
-      hipLaunchKernelGGL(multi_fma3_kernel<2>, dim3(grid, k), dim3(kStepBlock), 0, s, tab, nvec, a, b, p_scale, b_dev);
+  const int vec = Alignment().of(out, k).of(p, k).of(q, k).vec();
+  return for_body_and_tail<4>(Tail::kOwnLaunch, vec, d, kStepBlock, caps_of(2048), [&](auto width, const Span& sp) {
+    hipLaunchKernelGGL(multi_fma3_kernel<decltype(width)::value>, dim3(sp.grid, k), dim3(kStepBlock), 0, s,
+                       tab.advanced(sp.first), sp.count, a, b, p_scale, b_dev);
     BM_LAUNCH_CHECK();
-    body = nvec * vec;
-  }
-  if (body < d) {
-    Fma3Table tail = tab;
-    for (int i = 0; i < k; ++i) {
-      tail.out[i] += body;
-      tail.p[i] += body;
-      tail.q[i] += body;
-    }
-    const int64_t rest = d - body;
-    hipLaunchKernelGGL(multi_fma3_kernel<1>, dim3(stream_grid(rest, kStepBlock, 2048), k), dim3(kStepBlock), 0, s,
-                       tail, rest, a, b, p_scale, b_dev);
-    BM_LAUNCH_CHECK();
-  }
-  return 0;
+    return 0;
+  });
 }
 
 extern "C" int bm_multi_fma3(float* const* out, const float* const* p, const float* const* q, int k, int64_t d,
@@ -1295,32 +1261,14 @@ extern "C" int bm_multi_scale(float* const* y, int k, int64_t d, const float* fa
   if (d == 0) return 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
   ScaleTable tab{};
-  uintptr_t bits = 0;
-  for (int i = 0; i < k; ++i) {
-    tab.y[i] = y[i];
-    bits |= reinterpret_cast<uintptr_t>(y[i]);
-  }
-  const int vec = vec_of(bits);
-  int64_t body = 0;
-  if (vec >= 2 && d / vec > 0) {
-    const int64_t nvec = d / vec;
-    const int grid = stream_grid(nvec, kStepBlock, 2048);
-    if (vec == 4)
-      hipLaunchKernelGGL(multi_scale_kernel<4>, dim3(grid, k), dim3(kStepBlock), 0, s, tab, nvec, factors);
-    else
-      hipLaunchKernelGGL(multi_scale_kernel<2>, dim3(grid, k), dim3(kStepBlock), 0, s, tab, nvec, factors);
+  for (int i = 0; i < k; ++i) tab.y[i] = y[i];
+  const int vec = Alignment().of(y, k).vec();
+  return for_body_and_tail<4>(Tail::kOwnLaunch, vec, d, kStepBlock, caps_of(2048), [&](auto width, const Span& sp) {
+    hipLaunchKernelGGL(multi_scale_kernel<decltype(width)::value>, dim3(sp.grid, k), dim3(kStepBlock), 0, s,
+                       tab.advanced(sp.first), sp.count, factors);
     BM_LAUNCH_CHECK();
-    body = nvec * vec;
-  }
-  if (body < d) {
-    ScaleTable tail = tab;
-    for (int i = 0; i < k; ++i) tail.y[i] += body;
-    const int64_t rest = d - body;
-    hipLaunchKernelGGL(multi_scale_kernel<1>, dim3(stream_grid(rest, kStepBlock, 2048), k), dim3(kStepBlock), 0, s,
-                       tail, rest, factors);
-    BM_LAUNCH_CHECK();
-  }
-  return 0;
+    return 0;
+  });
 }
 
 extern "C" int bm_clip_factors(const double* row_sq, int k, float clip, float* factors_out, void* stream) {

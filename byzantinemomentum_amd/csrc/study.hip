@@ -45,7 +45,14 @@ struct StudyArgs {
   float* a_out;         // attack average, optional
   float* mom;           // momentum of the update (attack.py:836-838, --momentum-at update), or NULL: M <- fma(mom_b, defense, mom_a * M)
   float mom_a, mom_b;   // mu, 1 - dampening
+  StudyArgs advanced(int64_t by) const {
+    using bm::advanced;
+    return StudyArgs{advanced(s, by), advanced(h, by), advanced(def, by), advanced(byz, by), advanced(past, by),
+                     advanced(oldest, by), advanced(params, by), advanced(origin, by), advanced(curv, by),
+                     advanced(a_out, by), advanced(mom, by), mom_a, mom_b};
+  }
 };
+constexpr Caps kStudyCaps = caps_of(kStudyMaxBlocks);
 
 // CM: 0 no curvature term kept (nb_past = 0); 1 first step: C <- s, no dot with the past;
 //     2 C <- fma(1, s, mu * C); 3 C <- fma(1, s, mu * fma(w, oldest, C)) with w = -(mu^(P-1))
@@ -476,7 +483,9 @@ static int launch_study(const StudyArgs& a, bool att, bool l2, int cm, int vec, 
             : launch_study_cm<false, false>(a, cm, vec, f_real, mu, w, n, grid, partial, s);
 }
 
-int64_t study_workspace_bytes() { return (int64_t)(kStudyMaxBlocks + 1) * kStudyPartial * (int64_t)sizeof(double); }
+// (the partial layout is [slot][kStudyMaxBlocks + 1 workgroups], see study_stats_kernel)
+static_assert(kStudyCaps.sets() == kStudyMaxBlocks + 1, "bm_study_stats: partial sets and slot stride differ");
+int64_t study_workspace_bytes() { return (int64_t)kStudyCaps.sets() * kStudyPartial * (int64_t)sizeof(double); }
 
 }  // namespace bm
 
@@ -504,53 +513,25 @@ extern "C" int bm_study_stats_update(const float* sampled_avg, const float* hone
   StudyArgs a{sampled_avg, honest_avg, defense, att ? byz : nullptr, curv_mode >= 2 ? past_newest : nullptr,
               curv_mode == 3 ? past_oldest : nullptr, l2 ? params : nullptr, l2 ? origin : nullptr,
               curv_mode >= 1 ? curv : nullptr, att ? attack_avg_out : nullptr, update_momentum, momentum_mu, one_minus_damp};
-  const void* ptrs[11] = {a.s, a.h, a.def, a.byz, a.past, a.oldest, a.params, a.origin, a.curv, a.a_out, a.mom};
-  const int vec = common_vec_width(ptrs, 11, nullptr);  // null pointers do not constrain the width
+  const int vec = Alignment().of(a.s).of(a.h).of(a.def).of(a.byz).of(a.past).of(a.oldest).of(a.params).of(a.origin)
+                      .of(a.curv).of(a.a_out).of(a.mom).vec();
   double* partial = static_cast<double*>(ws);
   int nparts = 0;
-  int64_t body = 0;
-  int rc = 0;
-  if (vec >= 2 && d / vec > 0) {
-    const int64_t nvec = d / vec;
-    int grid;
-    if (study_burst_eligible(a, curv_mode, vec, nvec)) {
-      grid = compute_units();  // one workgroup of 1024 lanes per CU (<= kStudyMaxBlocks partial sets)
-      if (grid > kStudyMaxBlocks) grid = kStudyMaxBlocks;
+  const int rc = for_body_and_tail<4>(Tail::kOwnLaunch, vec, d, kStudyBlock, kStudyCaps, [&](auto width, Span& sp) {
+    constexpr int VEC = decltype(width)::value;
+    if (study_burst_eligible(a, curv_mode, VEC, sp.count)) {
+      sp.grid = compute_units();  // one workgroup of 1024 lanes per CU (<= kStudyMaxBlocks partial sets)
+      if (sp.grid > kStudyMaxBlocks) sp.grid = kStudyMaxBlocks;
       if (att)
-        rc = l2 ? launch_study_burst<true, true>(a, curv_mode, f_real, mu, oldest_weight, nvec, grid, partial, s)
-                : launch_study_burst<true, false>(a, curv_mode, f_real, mu, oldest_weight, nvec, grid, partial, s);
-      else
-        rc = l2 ? launch_study_burst<false, true>(a, curv_mode, f_real, mu, oldest_weight, nvec, grid, partial, s)
-                : launch_study_burst<false, false>(a, curv_mode, f_real, mu, oldest_weight, nvec, grid, partial, s);
-    } else {
-      grid = stream_grid(nvec, kStudyBlock, kStudyMaxBlocks);
-      rc = launch_study(a, att, l2, curv_mode, vec, f_real, mu, oldest_weight, nvec, grid, partial, s);
+        return l2 ? launch_study_burst<true, true>(a, curv_mode, f_real, mu, oldest_weight, sp.count, sp.grid, partial, s)
+                  : launch_study_burst<true, false>(a, curv_mode, f_real, mu, oldest_weight, sp.count, sp.grid, partial, s);
+      return l2 ? launch_study_burst<false, true>(a, curv_mode, f_real, mu, oldest_weight, sp.count, sp.grid, partial, s)
+                : launch_study_burst<false, false>(a, curv_mode, f_real, mu, oldest_weight, sp.count, sp.grid, partial, s);
     }
-    if (rc != 0) return rc;
-    nparts = grid;
-    body = nvec * vec;
-  }
-  if (body < d) {
-    StudyArgs t = a;
-    auto adv = [body](const float* p) { return p != nullptr ? p + body : nullptr; };
-    t.s = adv(a.s);
-    t.h = adv(a.h);
-    t.def = adv(a.def);
-    t.byz = adv(a.byz);
-    t.past = adv(a.past);
-    t.oldest = adv(a.oldest);
-    t.params = adv(a.params);
-    t.origin = adv(a.origin);
-    t.curv = a.curv != nullptr ? a.curv + body : nullptr;
-    t.a_out = a.a_out != nullptr ? a.a_out + body : nullptr;
-    t.mom = a.mom != nullptr ? a.mom + body : nullptr;
-    const int64_t rest = d - body;
-    const int grid = (body == 0) ? stream_grid(rest, kStudyBlock, kStudyMaxBlocks) : 1;
-    rc = launch_study(t, att, l2, curv_mode, 1, f_real, mu, oldest_weight, rest, grid,
-                      partial + nparts, s);
-    if (rc != 0) return rc;
-    nparts += grid;
-  }
+    return launch_study(a.advanced(sp.first), att, l2, curv_mode, VEC, f_real, mu, oldest_weight, sp.count, sp.grid,
+                        partial + sp.part, s);
+  }, &nparts);
+  if (rc != 0) return rc;
   // d == 0: no partial, the finish kernel writes zeros (every rank of a sharded job reaches its exchange)
   hipLaunchKernelGGL(study_finish_kernel, dim3(kStudyPartial), dim3(64), 0, s, partial, nparts, out);
   BM_LAUNCH_CHECK();

@@ -1,9 +1,11 @@
 """Register / spill / LDS figures of the gfx950 kernels inside libbm_gar.so (no GPU needed).
 
     python scripts/kernel_meta.py [regex on the demangled kernel name]
+    python scripts/kernel_meta.py diff LIB_A LIB_B      the proof that a host-only change left the device code alone
 
 Extracts the code objects with llvm-objdump --offloading into a temporary directory and reads the
 AMDGPU metadata notes (llvm-readelf --notes)."""
+import hashlib
 import pathlib
 import re
 import shutil
@@ -56,7 +58,44 @@ def packed_fp32(lib=LIB):
   return found
 
 
+def isa_hashes(lib=LIB):
+  """{kernel symbol: sha256 of its disassembled instruction text} over the gfx950 code objects of the library (a kernel
+  that several translation units hold, such as eval_finish_kernel, is keyed "symbol @ code object number")."""
+  text = {}
+  with tempfile.TemporaryDirectory() as tmp:
+    local = pathlib.Path(tmp) / pathlib.Path(lib).name
+    shutil.copy(lib, local)
+    subprocess.run([LLVM / "llvm-objdump", "--offloading", local], cwd=tmp, capture_output=True, check=True)
+    for number, co in enumerate(sorted(pathlib.Path(tmp).glob("*gfx950*"))):
+      dis = subprocess.run([LLVM / "llvm-objdump", "-d", "--no-show-raw-insn", "--no-leading-addr", co],
+                           capture_output=True, text=True, check=True).stdout
+      name = None
+      for line in dis.splitlines():
+        m = re.match(r"^[0-9a-f]* ?<(.+)>:$", line)
+        if m:
+          name = m.group(1) if m.group(1) not in text else f"{m.group(1)} @ {number}"
+          text[name] = []
+        elif name is not None and line.strip():
+          text[name].append(line.split("//")[0].strip())  # (the comment holds the address: where the kernel lies, not what it is)
+  return {k: hashlib.sha256("\n".join(v).encode()).hexdigest() for k, v in text.items()}
+
+
+def diff(lib_a, lib_b):
+  """Prints the kernel symbols only one library has and those whose instructions differ; returns their number."""
+  a, b = isa_hashes(lib_a), isa_hashes(lib_b)
+  only_a, only_b = sorted(set(a) - set(b)), sorted(set(b) - set(a))
+  changed = sorted(k for k in set(a) & set(b) if a[k] != b[k])
+  for title, names in (("only in A", only_a), ("only in B", only_b), ("instructions differ", changed)):
+    for nm in names:
+      print(f"{title}: {nm}")
+  print(f"A: {len(a)} kernel symbols, B: {len(b)}; only in A {len(only_a)}, only in B {len(only_b)}, "
+        f"instructions differ {len(changed)}")
+  return len(only_a) + len(only_b) + len(changed)
+
+
 if __name__ == "__main__":
+  if len(sys.argv) == 4 and sys.argv[1] == "diff":
+    sys.exit(1 if diff(sys.argv[2], sys.argv[3]) else 0)
   pat = re.compile(sys.argv[1]) if len(sys.argv) > 1 else None
   print(f"{'vgpr':>5} {'sgpr':>5} {'s_spill':>7} {'v_spill':>7} {'lds':>7} {'scratch':>7}  kernel")
   for k in kernels():

@@ -4,8 +4,8 @@ instance tests compare against (a helper module, not a conftest).
 A call's result depends on more than the rule and the row count: it runs in ONE of many compiled instances, chosen at
 run time and invisible to the caller, by
   * the row count N (one kernel per N = 1..64, colwise_dispatch.h; per (n, f) for Bulyan's pass 2, bulyan.hip),
-  * the vector width VEC = 4 / 2 / 1, the widest every row pointer and the output allow (common_vec_width,
-    bm_common.h) capped per instance by its `kMaxVec`,
+  * the vector width VEC = 4 / 2 / 1, the widest every row pointer and the output allow (Alignment,
+    launch_plan.h) capped per instance by its `kMaxVec`,
   * the launch form (plain grid-stride, or the burst form of the column kernels), and the BM_* tuning knobs.
 The per-column arithmetic is the same in every instance, so a column must give the same bits whichever instance
 computed it.
@@ -97,7 +97,7 @@ def burst_limit(rule):
 
 
 def vec_width(byte_offsets):
-  """common_vec_width: the widest vector every pointer allows (allocations themselves are 256-byte aligned)."""
+  """Alignment::vec (launch_plan.h): the widest vector every pointer allows (allocations themselves are 256-byte aligned)."""
   bits = 0
   for o in byte_offsets:
     bits |= o
@@ -136,7 +136,7 @@ def instances(case, cus=256):
   knobs = dict(DEFAULT_KNOBS, **dict(case.knobs))
   k = case.kernel
   if k == "colwise":
-    # launch_colwise_n / launch_colwise_vec: one launch per 2^29 columns, the d % VEC tail inside it
+    # launch_colwise_n / launch_colwise_vec: one launch per 2^29 columns, the d % VEC tail inside it (Tail::kRides, launch_plan.h)
     vec = min(vec_width(row_offsets(case.offset, case.n)), colwise_max_vec(case.rule, case.n))
     if vec == 4 and case.n > 28 and knobs["BM_COL_WIDE"] == 0:
       vec = 2

@@ -287,7 +287,8 @@ def test_order_pair_every_instance(bm, cus):
 
 def test_sums_of_squares_and_axpby_at_every_width(bm, cus):
   """bm_sqdist2 and bm_row_sqnorms against float64 (1e-6), bm_multi_axpby against a float64 axpby rounded to fp32
-  (1e-6), at rows of 0 / 4 / 8 bytes and a mix."""
+  (1e-6), at rows of 0 / 4 / 8 bytes and a mix; so bm_multi_dot (1e-6 of |a| |b|), bm_multi_fma3 with its factor as a
+  number and in device memory (1e-6) and bm_multi_scale (a power of two: exact; a factor 1: untouched)."""
   d = 300007
   gen = torch.Generator(device=DEV).manual_seed(3)
   vals = (1.0 + torch.arange(6, device=DEV)[:, None]) * torch.randn(6, d, device=DEV, generator=gen)
@@ -299,18 +300,36 @@ def test_sums_of_squares_and_axpby_at_every_width(bm, cus):
     got = bm.stats.row_sqnorms(rows).tolist()
     for g, w in zip(got, v64.pow(2).sum(dim=1).tolist()):
       assert abs(g - w) <= 1e-6 * w, (off, g, w)
+    gram, extra = bm.stats.study_dots(rows[:2], rows[2:4])
+    norm = v64.pow(2).sum(dim=1).sqrt().tolist()
+    for i in range(2):
+      for j in range(2):
+        assert abs(gram[i, j].item() - torch.dot(v64[i], v64[j]).item()) <= 1e-6 * norm[i] * norm[j], (off, i, j)
+      assert abs(extra[i].item() - torch.dot(v64[0], v64[2 + i]).item()) <= 1e-6 * norm[0] * norm[2 + i], (off, i)
+    for b in (0.1, torch.tensor([0.1], dtype=torch.float64, device=DEV)):
+      outs = M.place(torch.zeros(2, d, device=DEV), off)
+      bm.stats.multi_fma3(outs, rows[:2], rows[2:4], 0.99, b)
+      for i, o in enumerate(outs):
+        want = (0.99 * v64[i] + 0.1 * v64[2 + i]).float()
+        assert bool(M.check_close(o.cpu(), want.cpu(), 1e-6, float(want.abs().max())).all()), (off, i)
     ys, xs = rows[:3], rows[3:]
     bm.stats.multi_axpby(ys, xs, 0.99, 0.1)
     for y, i in zip(ys, range(3)):
       want = (0.99 * v64[i] + 0.1 * v64[3 + i]).float()
       ok = M.check_close(y.cpu(), want.cpu(), 1e-6, float(want.abs().max()))
       assert bool(ok.all()), (off, i)
+    factors = torch.ones(64, device=DEV)
+    factors[0] = 0.5
+    bm.stats.multi_scale(rows[4:], factors)
+    assert torch.equal(rows[4], 0.5 * vals[4]) and torch.equal(rows[5], vals[5]), off
 
 
 @pytest.mark.parametrize("n", [3, 11, 25, 51, 64])
 def test_means_and_statistics_at_every_width(bm, cus, n):
   """average, Krum and CGE (the selected-mean kernel) and the statistics pass at rows of 0 / 4 / 8 bytes and mixed, at
-  the bars of test_unaligned_rows_and_tails."""
+  the bars of test_unaligned_rows_and_tails; the first pass of a step (bm_momentum_stats, the rows as sampled gradients
+  and as many buffers, 63 at most) at the bars of test_momentum_stats_kernel_tiers, and the study block (bm_study_stats_update) at
+  those of test_study_stats_against_fp64."""
   f = {3: 0, 11: 2, 25: 5, 51: 12, 64: 15}[n]
   d = 4099
   rows, h = O.make_stack("hetero", n, f, d, seed=41 * n)
@@ -319,6 +338,14 @@ def test_means_and_statistics_at_every_width(bm, cus, n):
   want_krum, want_avg, want_cge = O.krum(rows, f), O.average(rows), O.cge(rows, f)
   wavg, wnorm, wdev, wmx = O.compute_avg_dev_max(rows, "f64")
   want_stats_avg = O.compute_avg_dev_max(rows)[0]
+  gen = torch.Generator().manual_seed(5 * n)
+  hb = min(n, 63)  # (the wrapper validates the buffers and one gradient as one list of at most 64)
+  bufs = torch.randn(hb, d, generator=gen)
+  want_bufs = [b.clone().mul_(0.9).add_(g, alpha=0.1) for b, g in zip(bufs, rows)]
+  wh_avg, wh_norm, wh_dev, wh_max = O.compute_avg_dev_max(want_bufs, "f64")
+  want_h_avg = O.compute_avg_dev_max(want_bufs)[0]
+  study = torch.randn(10, d, generator=gen).to(DEV)   # s, h, defense, byz, past, oldest, params, origin, C, M
+  s64 = study.double()
   for off in M.OFFSETS:
     dev = M.rows_of(M.place(distinct, off), rowmap)
     bm.gars.invalidate_rank_cache()
@@ -329,3 +356,32 @@ def test_means_and_statistics_at_every_width(bm, cus, n):
     avg, norm, devi, mx = bm.compute_avg_dev_max(dev)
     assert torch.equal(avg.cpu(), want_stats_avg), (n, off)
     assert abs(norm - wnorm) <= 1e-6 * wnorm and abs(devi - wdev) <= 1e-6 * wdev and abs(mx - wmx) <= 1e-6 * wmx
+    dbufs = M.place(bufs.to(DEV), off)
+    s_avg, h_avg, _, out6 = bm.stats.momentum_stats(dev, dbufs, 0.9, 0.1)
+    for a, b in zip(dbufs, want_bufs):
+      assert float((a.cpu() - b).abs().max()) <= 1e-6 * float(b.abs().max()), (n, off)
+    assert torch.equal(s_avg.cpu(), want_stats_avg), (n, off)
+    assert float((h_avg.cpu() - want_h_avg).abs().max()) <= 2e-7 * wh_max, (n, off)
+    o = out6.tolist()
+    for got, want in ((math.sqrt(o[0]), wnorm), (math.sqrt(o[1] / (n - 1)), wdev), (o[2], wmx),
+                      (math.sqrt(o[3]), wh_norm), (math.sqrt(o[4] / (hb - 1)), wh_dev), (o[5], wh_max)):
+      assert abs(got - want) <= 1e-5 * want, (n, off, got, want)
+    s, h, df, byz, past, old, par, org, curv, mom = M.place(study, off)
+    mu, w = 0.9, -(0.9 ** 4)
+    out = bm.stats.study_stats(s, h, df, byz, 2, past_newest=past, curv=curv, past_oldest=old, curv_mode=3, mu=mu,
+                               oldest_weight=w, params=par, origin=org, update_momentum=mom, update_mu=0.9,
+                               update_omd=0.1).tolist()
+    c64 = [s64[0], s64[1], s64[2], ((study[3] + study[3]) / torch.full_like(study[3], 2.0)).double()]
+    for i in range(4):
+      for j in range(4):
+        scale = math.sqrt(float(c64[i].pow(2).sum()) * float(c64[j].pow(2).sum()))
+        assert abs(out[4 * i + j] - float(torch.dot(c64[i], c64[j]))) <= 1e-6 * scale, (n, off, i, j)
+    for slot, other in ((16, s64[4]), (17, s64[8])):
+      scale = math.sqrt(float(c64[0].pow(2).sum()) * float(other.pow(2).sum()))
+      assert abs(out[slot] - float(torch.dot(c64[0], other))) <= 1e-6 * scale, (n, off, slot)
+    want_l2 = float((s64[6] - s64[7]).pow(2).sum())
+    assert abs(out[22] - want_l2) <= 1e-6 * want_l2 and out[21] == float(study[2].abs().max()), (n, off)
+    want_c = study[0] + mu * torch.addcmul(study[8], torch.full_like(study[5], w), study[5])  # fma(w, oldest, C)
+    assert float((curv - want_c).abs().max()) <= 2e-7 * float(want_c.abs().max()), (n, off)
+    want_m = (0.1 * s64[2] + 0.9 * s64[9]).float()
+    assert bool(M.check_close(mom.cpu(), want_m.cpu(), 1e-6, float(want_m.abs().max())).all()), (n, off)

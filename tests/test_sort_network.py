@@ -120,14 +120,14 @@ int main() {
       for (int j = i; j < n; ++j) printf(" %d", bm::b3_tri_index(i, j, n));
     printf("\n");
   }
-  // launch-shape helpers of bm_common.h
+  // launch-shape helpers of launch_plan.h
   printf("grid %d %d %d %d\n", bm::stream_grid(0, 256, 16384), bm::stream_grid(1, 256, 16384),
          bm::stream_grid(257, 256, 16384), bm::stream_grid((int64_t)1 << 40, 256, 16384));
   const void* p[3] = {(void*)0x1000, (void*)0x2010, (void*)0x3020};
   const void* q[2] = {(void*)0x1008, (void*)0x2010};
   const void* r[2] = {(void*)0x1004, (void*)0x2010};
-  printf("vec %d %d %d %d\n", bm::common_vec_width(p, 3, nullptr), bm::common_vec_width(q, 2, nullptr),
-         bm::common_vec_width(r, 2, nullptr), bm::common_vec_width(p, 3, (void*)0x4004));
+  printf("vec %d %d %d %d\n", bm::Alignment().of(p, 3).vec(), bm::Alignment().of(q, 2).vec(),
+         bm::Alignment().of(r, 2).vec(), bm::Alignment().of(p, 3).of((void*)0x4004).vec());
   return 0;
 }
 '''
@@ -136,7 +136,7 @@ int main() {
 def test_triangle_index_and_launch_helpers_of_the_headers(tmp_path):
   """b3_tri_index (csrc/gram_split.h) — where the Gram kernel, its reduction and the distance kernel all look up entry
   (i, j) of the compact upper triangle — is a bijection onto 0 .. n(n+1)/2 - 1 in row-major order for every n <= 64;
-  stream_grid and common_vec_width (csrc/bm_common.h) answer as documented.  Host-only compilation of the headers."""
+  stream_grid and Alignment (csrc/launch_plan.h) answer as documented.  Host-only compilation of the headers."""
   hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
   if not pathlib.Path(hipcc).exists():
     pytest.skip("hipcc not here")
