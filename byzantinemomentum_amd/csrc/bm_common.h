@@ -270,6 +270,16 @@ __device__ __forceinline__ double block_reduce_sum(double v, double* lds /* BLOC
   return r;
 }
 
+// One coordinate of the Byzantine vector of the "identical" attacks (attacks/identical.py:63-86,129-141) from its
+// column's average over k rows and two-pass deviation sum q:
+//   empire: grad_att = grad_avg.neg();  little: grad_att = grad_stck.var(dim=0).sqrt_();  grad_att.mul_(factor)
+//   byz_grad = grad_avg.add_(grad_att);  BM_ATTACK_DIRECTION: grad_att alone
+__device__ __forceinline__ float byzantine_coordinate(float avg, float q, float fk, float scale, int attack_kind) {
+  const float dir = ((attack_kind & 15) == BM_ATTACK_LITTLE) ? __builtin_sqrtf(q / (fk - 1.0f)) : -avg;
+  const float att = dir * scale;
+  return (attack_kind & BM_ATTACK_DIRECTION) ? att : avg + att;
+}
+
 }  // namespace bm
 
 namespace bm {

@@ -196,13 +196,7 @@ __global__ __launch_bounds__(kRedBlock) void stack_stats_kernel(RowTable rows, i
     if (scaled_out != nullptr) {
       float sc[VEC];
 #pragma unroll
-      for (int c = 0; c < VEC; ++c) {
-        // empire: grad_att = grad_avg.neg();            little: grad_att = grad_stck.var(dim=0).sqrt_()
-        const float dir = ((attack_kind & 15) == BM_ATTACK_LITTLE) ? __builtin_sqrtf(colq[c] / (fk - 1.0f)) : -avg[c];
-        const float att = dir * scale;  // grad_att.mul_(factor)
-        // byz_grad = grad_avg.add_(grad_att); BM_ATTACK_DIRECTION: grad_att alone
-        sc[c] = (attack_kind & BM_ATTACK_DIRECTION) ? att : avg[c] + att;
-      }
+      for (int c = 0; c < VEC; ++c) sc[c] = byzantine_coordinate(avg[c], colq[c], fk, scale, attack_kind);
       store_result_policy<VEC>(scaled_out + v * VEC, sc, nt_result);
     }
   }

@@ -57,6 +57,30 @@ __device__ __forceinline__ float block_reduce_absmax(float m, float* lds) {
   return r;
 }
 
+// The epilogue of the two register-resident kernels of the first pass: a workgroup's six fp64 partials (slots 0,1,3,4
+// sums, 2 and 5 NaN-propagating maxima) from its lanes' accumulators.
+template <int BLOCK>
+__device__ __forceinline__ void store_step_partials(float n2s, float dvs, float mxs, float n2h, float dvh, float mxh, bool nan_s,
+                                                    bool nan_h, double* red, float* mred, double* __restrict__ partial) {
+  if (nan_s) mxs = __builtin_nanf("");  // torch's abs().max() propagates NaN; fmaxf does not
+  if (nan_h) mxh = __builtin_nanf("");
+  const double r0 = block_reduce_sum<BLOCK>((double)n2s, red);
+  const double r1 = block_reduce_sum<BLOCK>((double)dvs, red);
+  const double r3 = block_reduce_sum<BLOCK>((double)n2h, red);
+  const double r4 = block_reduce_sum<BLOCK>((double)dvh, red);
+  const float r2 = block_reduce_absmax<BLOCK>(mxs, mred);
+  const float r5 = block_reduce_absmax<BLOCK>(mxh, mred);
+  if (threadIdx.x == 0) {
+    double* p = partial + (int64_t)blockIdx.x * 6;
+    p[0] = r0;
+    p[1] = r1;
+    p[2] = (double)r2;
+    p[3] = r3;
+    p[4] = r4;
+    p[5] = (double)r5;
+  }
+}
+
 // Register-resident form (max(ks, h) <= T <= 20): the ks + h values of a column group stay in VGPRs, so the deviations
 // are two-pass (no cancellation) without re-reading anything.
 //   EXACT  ks == h == T: no row predicate is left in the code (the C5 shape: 20 sampled gradients, 20 buffers)
@@ -174,10 +198,7 @@ __global__ __launch_bounds__(BURST ? kStepBurstBlock : kStepBlock) void momentum
             qh = __builtin_fmaf(df, df, qh);
           }
         dvh += qh;
-        // empire: grad_att = grad_avg.neg();  little: grad_att = grad_stck.var(dim=0).sqrt_()
-        const float dir = ((attack_kind & 15) == BM_ATTACK_LITTLE) ? __builtin_sqrtf(qh / (fh - 1.0f)) : -t;
-        const float att = dir * scale;  // grad_att.mul_(factor)
-        bz[c] = (attack_kind & BM_ATTACK_DIRECTION) ? att : t + att;  // byz_grad = grad_avg.add_(grad_att)
+        bz[c] = byzantine_coordinate(t, qh, fh, scale, attack_kind);
         if constexpr (RULE >= 0) {  // defense = GAR(honests + [byz] * NB) for this column (attack.py:821)
           float x[T + NB];
 #pragma unroll
@@ -203,23 +224,7 @@ __global__ __launch_bounds__(BURST ? kStepBurstBlock : kStepBlock) void momentum
       if constexpr (RULE >= 0) store_stream_off<VEC>(defense_out, off, df);
     }
   }
-  if (nan_s) mxs = __builtin_nanf("");  // torch's abs().max() propagates NaN; fmaxf does not
-  if (nan_h) mxh = __builtin_nanf("");
-  const double r0 = block_reduce_sum<BLOCK>((double)n2s, red);
-  const double r1 = block_reduce_sum<BLOCK>((double)dvs, red);
-  const double r3 = block_reduce_sum<BLOCK>((double)n2h, red);
-  const double r4 = block_reduce_sum<BLOCK>((double)dvh, red);
-  const float r2 = block_reduce_absmax<BLOCK>(mxs, mred);
-  const float r5 = block_reduce_absmax<BLOCK>(mxh, mred);
-  if (threadIdx.x == 0) {
-    double* p = partial + (int64_t)blockIdx.x * 6;
-    p[0] = r0;
-    p[1] = r1;
-    p[2] = (double)r2;
-    p[3] = r3;
-    p[4] = r4;
-    p[5] = (double)r5;
-  }
+  store_step_partials<BLOCK>(n2s, dvs, mxs, n2h, dvh, mxh, nan_s, nan_h, red, mred, partial);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -356,9 +361,7 @@ __global__ __launch_bounds__(kStepBurstBlock) void momentum_gram_kernel(
           qh = __builtin_fmaf(df, df, qh);
         }
         dvh += qh;
-        const float dir = ((attack_kind & 15) == BM_ATTACK_LITTLE) ? __builtin_sqrtf(qh / (fh - 1.0f)) : -t;
-        const float att = dir * scale;
-        bz[c] = (attack_kind & BM_ATTACK_DIRECTION) ? att : t + att;
+        bz[c] = byzantine_coordinate(t, qh, fh, scale, attack_kind);
       }
     }
     // ---- the Gram of the centred rows (20 updated buffers + the Byzantine row), two halves of 128 coordinates ----
@@ -436,23 +439,7 @@ __global__ __launch_bounds__(kStepBurstBlock) void momentum_gram_kernel(
       store_stream_off<VEC>(byz_out, off, bz);
     }
   }
-  if (nan_s) mxs = __builtin_nanf("");
-  if (nan_h) mxh = __builtin_nanf("");
-  const double r0 = block_reduce_sum<BLOCK>((double)n2s, red);
-  const double r1 = block_reduce_sum<BLOCK>((double)dvs, red);
-  const double r3 = block_reduce_sum<BLOCK>((double)n2h, red);
-  const double r4 = block_reduce_sum<BLOCK>((double)dvh, red);
-  const float r2 = block_reduce_absmax<BLOCK>(mxs, mred);
-  const float r5 = block_reduce_absmax<BLOCK>(mxh, mred);
-  if (threadIdx.x == 0) {
-    double* p = partial + (int64_t)blockIdx.x * 6;
-    p[0] = r0;
-    p[1] = r1;
-    p[2] = (double)r2;
-    p[3] = r3;
-    p[4] = r4;
-    p[5] = (double)r5;
-  }
+  store_step_partials<BLOCK>(n2s, dvs, mxs, n2h, dvh, mxh, nan_s, nan_h, red, mred, partial);
   // ---- workgroup reduction of the partial Gram, fixed order; compact upper triangle of the 21 x 21 matrix ----
   // C/D layout of the 16x16 MFMA: lane l, register v -> row 4*(l>>4)+v, column l&15.
   double* gred = reinterpret_cast<double*>(sg_smem);  // [waves][256], aliases the planes
@@ -595,14 +582,14 @@ __global__ __launch_bounds__(kStepBlock, 4) void momentum_stats_stream_kernel(
       float colq = __builtin_fmaf(eh, __builtin_fmaf(fh, eh, -2.0f * th[c]), qh[c]);
       colq = colq < 0.0f ? 0.0f : colq;  // rounding of a column whose rows coincide; NaN stays NaN
       dvh += colq;
-      const float dir = ((attack_kind & 15) == BM_ATTACK_LITTLE) ? __builtin_sqrtf(colq / (fh - 1.0f)) : -t;
-      const float att = dir * scale;
-      r_bz[c] = (attack_kind & BM_ATTACK_DIRECTION) ? att : t + att;
+      r_bz[c] = byzantine_coordinate(t, colq, fh, scale, attack_kind);
     }
     if (s_avg_out != nullptr) store_stream_off<VEC>(s_avg_out, off, r_sa);
     if (h_avg_out != nullptr) store_stream_off<VEC>(h_avg_out, off, r_ha);
     if (byz_out != nullptr) store_stream_off<VEC>(byz_out, off, r_bz);
   }
+  // (its own copy of store_step_partials, with the sampled deviation sum clamped at zero: through the helper the
+  // compiler orders this kernel's loop differently at 8- and 16-byte columns)
   if (nan_s) mxs = __builtin_nanf("");
   if (nan_h) mxh = __builtin_nanf("");
   const double r0 = block_reduce_sum<kStepBlock>((double)n2s, red);
@@ -682,53 +669,99 @@ __global__ __launch_bounds__(kFinishThreads) void step_finish_kernel(const doubl
   }
 }
 
-template <int T, int VEC, bool EXACT, bool CLIP>
-static int launch_momentum_stats_form(const StepTable& tab, int ks, int h, int64_t nvec, float mu, float omd,
-                                      const float* clipf, float* s_avg, float* h_avg, float* byz, float scale,
-                                      int kind, double* partial, int* grid_io, hipStream_t s) {
-  // burst form: one workgroup per CU, once every CU has BM_STEP_BURST (default 8) iterations to alternate over
-  const int cus = compute_units();
-  const int64_t burst_iters = nvec / ((int64_t)cus * kStepBurstBlock);
-  if (tuning().step_burst > 0 && burst_iters >= tuning().step_burst && cus < *grid_io) {
-    *grid_io = cus;
-    hipLaunchKernelGGL((momentum_stats_kernel<T, VEC, EXACT, CLIP, true>), dim3(cus), dim3(kStepBurstBlock), 0, s, tab,
-                       ks, h, (uint32_t)nvec, mu, omd, clipf, s_avg, h_avg, byz, scale, kind, partial, 0, 0.0f, nullptr);
-  } else {
-    hipLaunchKernelGGL((momentum_stats_kernel<T, VEC, EXACT, CLIP, false>), dim3(*grid_io), dim3(kStepBlock), 0, s, tab,
-                       ks, h, (uint32_t)nvec, mu, omd, clipf, s_avg, h_avg, byz, scale, kind, partial, 0, 0.0f, nullptr);
+// What every launcher of the first pass passes on.  An entry point fills one for its whole pass; at(span) is one launch's.
+struct StepArgs {
+  StepTable tab;
+  int ks, h;
+  int64_t nvec;
+  float mu, omd;
+  const float* clipf;
+  float *s_avg, *h_avg, *byz;
+  float scale;
+  int kind;
+  double* partial;  // the workspace: six doubles per workgroup
+  int* grid_io;     // in = the grid of the plain form, out = the number of workgroups launched (= partial sets written)
+  hipStream_t s;
+  bool nomom = false;  // no momentum buffers (tab.b is null): the honest rows are the sampled rows
+  int rule_f = 0;      // the rule riding along (launch_fused_rule_any fills these three), else unused
+  float rule_inv_keep = 0.0f;
+  float* defense = nullptr;
+  StepArgs moved(int64_t by) const {
+    StepArgs a = *this;
+    a.tab = tab.advanced(by);
+    a.s_avg = advanced(s_avg, by);
+    a.h_avg = advanced(h_avg, by);
+    a.byz = advanced(byz, by);
+    return a;
   }
+  StepArgs at(Span& sp) const {
+    StepArgs a = moved(sp.first);
+    a.nvec = sp.count;
+    a.partial = partial + (int64_t)sp.part * 6;
+    a.grid_io = &sp.grid;
+    return a;
+  }
+};
+
+// Row tables of a pass, padded with their last row: the streaming kernel loads whole batches unconditionally.
+// buffers == nullptr: no momentum, b[] stays null and is never dereferenced.
+static StepTable make_step_table(const float* const* sampled, int ks, float* const* buffers, int h) {
+  StepTable tab{};
+  for (int i = 0; i < BM_MAX_ROWS; ++i) {
+    tab.g[i] = sampled[i < ks ? i : ks - 1];
+    if (buffers != nullptr) tab.b[i] = buffers[i < h ? i : h - 1];
+  }
+  return tab;
+}
+
+// burst forms: one workgroup per CU, once every CU has BM_STEP_BURST (default 8) iterations to alternate over
+static bool burst_ready(int64_t nvec, int cus) {
+  return tuning().step_burst > 0 && nvec / ((int64_t)cus * kStepBurstBlock) >= tuning().step_burst;
+}
+
+static bool is_column_rule(int op) {
+  return op == BM_OP_MEDIAN || op == BM_OP_TRMEAN || op == BM_OP_PHOCAS || op == BM_OP_MEAMED;
+}
+// empire / little, with or without BM_ATTACK_DIRECTION
+static bool is_identical_attack(int kind) {
+  return (kind & ~BM_ATTACK_DIRECTION) == BM_ATTACK_EMPIRE || (kind & ~BM_ATTACK_DIRECTION) == BM_ATTACK_LITTLE;
+}
+
+template <class Kernel>
+static int launch_momentum_stats_kernel(Kernel kernel, int grid, int block, const StepArgs& a) {
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, a.s, a.tab, a.ks, a.h, (uint32_t)a.nvec, a.mu, a.omd, a.clipf,
+                     a.s_avg, a.h_avg, a.byz, a.scale, a.kind, a.partial, a.rule_f, a.rule_inv_keep, a.defense);
   BM_LAUNCH_CHECK();
   return 0;
 }
 
-// *grid_io: in = the grid of the plain form, out = the number of workgroups launched (= partial sets written)
-template <int T, int VEC>
-static int launch_momentum_stats(const StepTable& tab, int ks, int h, int64_t nvec, float mu, float omd,
-                                 const float* clipf, float* s_avg, float* h_avg, float* byz, float scale, int kind,
-                                 double* partial, int* grid_io, hipStream_t s) {
-#define BM_STEP_FORM(EX, CL) \
-  launch_momentum_stats_form<T, VEC, EX, CL>(tab, ks, h, nvec, mu, omd, clipf, s_avg, h_avg, byz, scale, kind, partial, grid_io, s)
-  const bool exact = (ks == T && h == T);
-  if constexpr (T > 12) {  // with row predicates the 2 x 20 x VEC values no longer fit: the dispatcher sends those shapes elsewhere
-    if (!exact) return BM_EINVAL;
-    return clipf != nullptr ? BM_STEP_FORM(true, true) : BM_STEP_FORM(true, false);
-  } else {
-    if (clipf != nullptr) return exact ? BM_STEP_FORM(true, true) : BM_STEP_FORM(false, true);
-    return exact ? BM_STEP_FORM(true, false) : BM_STEP_FORM(false, false);
+template <int T, int VEC, bool EXACT, bool CLIP, int RULE = -1, int NB = 0, bool NOMOM = false>
+static int launch_momentum_stats_form(const StepArgs& a) {
+  const int cus = compute_units();
+  if (burst_ready(a.nvec, cus) && cus < *a.grid_io) {
+    *a.grid_io = cus;
+    return launch_momentum_stats_kernel(momentum_stats_kernel<T, VEC, EXACT, CLIP, true, RULE, NB, NOMOM>, cus, kStepBurstBlock, a);
   }
-#undef BM_STEP_FORM
+  return launch_momentum_stats_kernel(momentum_stats_kernel<T, VEC, EXACT, CLIP, false, RULE, NB, NOMOM>, *a.grid_io, kStepBlock, a);
 }
 
 template <int T, int VEC>
-static int launch_momentum_stats_stream(const StepTable& tab, int ks, int h, int64_t nvec, float mu, float omd,
-                                        const float* clipf, float* s_avg, float* h_avg, float* byz, float scale,
-                                        int kind, double* partial, int* grid_io, hipStream_t s) {
-  if (clipf != nullptr)
-    hipLaunchKernelGGL((momentum_stats_stream_kernel<T, VEC, true>), dim3(*grid_io), dim3(kStepBlock), 0, s, tab, ks, h,
-                       (uint32_t)nvec, mu, omd, clipf, s_avg, h_avg, byz, scale, kind, partial);
-  else
-    hipLaunchKernelGGL((momentum_stats_stream_kernel<T, VEC, false>), dim3(*grid_io), dim3(kStepBlock), 0, s, tab, ks, h,
-                       (uint32_t)nvec, mu, omd, clipf, s_avg, h_avg, byz, scale, kind, partial);
+static int launch_momentum_stats(const StepArgs& a) {
+  const bool exact = (a.ks == T && a.h == T);
+  if constexpr (T > 12) {  // with row predicates the 2 x 20 x VEC values no longer fit: the dispatcher sends those shapes elsewhere
+    if (!exact) return BM_EINVAL;
+    return a.clipf != nullptr ? launch_momentum_stats_form<T, VEC, true, true>(a) : launch_momentum_stats_form<T, VEC, true, false>(a);
+  } else {
+    if (a.clipf != nullptr) return exact ? launch_momentum_stats_form<T, VEC, true, true>(a) : launch_momentum_stats_form<T, VEC, false, true>(a);
+    return exact ? launch_momentum_stats_form<T, VEC, true, false>(a) : launch_momentum_stats_form<T, VEC, false, false>(a);
+  }
+}
+
+template <int T, int VEC>
+static int launch_momentum_stats_stream(const StepArgs& a) {
+  auto kernel = a.clipf != nullptr ? momentum_stats_stream_kernel<T, VEC, true> : momentum_stats_stream_kernel<T, VEC, false>;
+  hipLaunchKernelGGL(kernel, dim3(*a.grid_io), dim3(kStepBlock), 0, a.s, a.tab, a.ks, a.h, (uint32_t)a.nvec, a.mu, a.omd,
+                     a.clipf, a.s_avg, a.h_avg, a.byz, a.scale, a.kind, a.partial);
   BM_LAUNCH_CHECK();
   return 0;
 }
@@ -737,22 +770,18 @@ static int launch_momentum_stats_stream(const StepTable& tab, int ks, int h, int
 // T = 8, 12, 14, 20) it fits two waves per SIMD up to T = 20, with them up to T = 12; every other shape takes the streaming
 // form, whose footprint does not depend on the number of rows.
 template <int VEC>
-static int dispatch_momentum_stats(const StepTable& tab, int ks, int h, int64_t nvec, float mu, float omd,
-                                   const float* clipf, float* s_avg, float* h_avg, float* byz, float scale, int kind,
-                                   double* partial, int* grid_io, hipStream_t s) {
-  const int t = ks > h ? ks : h;
-#define BM_STEP_ARGS tab, ks, h, nvec, mu, omd, clipf, s_avg, h_avg, byz, scale, kind, partial, grid_io, s
+static int dispatch_momentum_stats(const StepArgs& a) {
+  const int ks = a.ks, h = a.h, t = ks > h ? ks : h;
   // BM_STEP_STREAM=1: the streaming form at every size (tests, experiments)
   if (tuning().step_stream != 1) {
-    if (t <= 8) return launch_momentum_stats<8, VEC>(BM_STEP_ARGS);
-    if (t <= 12) return launch_momentum_stats<12, VEC>(BM_STEP_ARGS);
-    if (ks == 14 && h == 14) return launch_momentum_stats<14, VEC>(BM_STEP_ARGS);  // n = 25, f = 11 (reproduce.py:181)
-    if (ks == 20 && h == 20) return launch_momentum_stats<20, VEC>(BM_STEP_ARGS);  // n = 25, f = 5
+    if (t <= 8) return launch_momentum_stats<8, VEC>(a);
+    if (t <= 12) return launch_momentum_stats<12, VEC>(a);
+    if (ks == 14 && h == 14) return launch_momentum_stats<14, VEC>(a);  // n = 25, f = 11 (reproduce.py:181)
+    if (ks == 20 && h == 20) return launch_momentum_stats<20, VEC>(a);  // n = 25, f = 5
   }
-  if (t <= 20) return launch_momentum_stats_stream<20, VEC>(BM_STEP_ARGS);
-  if (t <= 40) return launch_momentum_stats_stream<40, VEC>(BM_STEP_ARGS);
-  return launch_momentum_stats_stream<64, VEC>(BM_STEP_ARGS);
-#undef BM_STEP_ARGS
+  if (t <= 20) return launch_momentum_stats_stream<20, VEC>(a);
+  if (t <= 40) return launch_momentum_stats_stream<40, VEC>(a);
+  return launch_momentum_stats_stream<64, VEC>(a);
 }
 
 // ---------------------------------------------------------------------------
@@ -837,40 +866,21 @@ __global__ __launch_bounds__(64) void clip_factors_kernel(const double* __restri
 }
 
 // ---------------------------------------------------------------------------
-// First pass + coordinate-wise rule in one kernel (median / trimmed mean over the h = 20 updated buffers and 1..6
-// copies of the Byzantine vector: the C5 shape and its neighbours).  Returns false when no instance fits.
+// First pass + coordinate-wise rule in one kernel (median / trimmed mean / phocas / meamed over the h = T updated buffers
+// and NB copies of the Byzantine vector): the register-resident form at ks = h = T with the rule's template arguments.
 // ---------------------------------------------------------------------------
 template <int T, int RULE, int NB, bool CLIP, bool NOMOM = false>
-static void launch_fused_rule(const StepTable& tab, int64_t nvec, float mu, float omd, const float* clipf, float* s_avg,
-                              float* h_avg, float* byz, float scale, int kind, double* partial, int rule_f,
-                              float* defense, int* grid_io, hipStream_t s) {
+static int launch_fused_rule(StepArgs a) {
   constexpr int N = T + NB;
-  const int keep = (RULE == BM_OP_TRMEAN) ? (N - 2 * rule_f) : ((RULE == BM_OP_PHOCAS || RULE == BM_OP_MEAMED) ? (N - rule_f) : N);
-  const float inv_keep = 1.0f / (float)(keep > 0 ? keep : 1);
-  const int cus = compute_units();
-  const int64_t burst_iters = nvec / ((int64_t)cus * kStepBurstBlock);
-  if (tuning().step_burst > 0 && burst_iters >= tuning().step_burst && cus < *grid_io) {
-    *grid_io = cus;
-    hipLaunchKernelGGL((momentum_stats_kernel<T, 4, true, CLIP, true, RULE, NB, NOMOM>), dim3(cus), dim3(kStepBurstBlock), 0,
-                       s, tab, T, T, (uint32_t)nvec, mu, omd, clipf, s_avg, h_avg, byz, scale, kind, partial,
-                       rule_f, inv_keep, defense);
-  } else {
-    hipLaunchKernelGGL((momentum_stats_kernel<T, 4, true, CLIP, false, RULE, NB, NOMOM>), dim3(*grid_io), dim3(kStepBlock), 0,
-                       s, tab, T, T, (uint32_t)nvec, mu, omd, clipf, s_avg, h_avg, byz, scale, kind, partial,
-                       rule_f, inv_keep, defense);
-  }
+  const int keep = (RULE == BM_OP_TRMEAN) ? (N - 2 * a.rule_f) : ((RULE == BM_OP_PHOCAS || RULE == BM_OP_MEAMED) ? (N - a.rule_f) : N);
+  a.rule_inv_keep = 1.0f / (float)(keep > 0 ? keep : 1);
+  return launch_momentum_stats_form<T, 4, true, CLIP, RULE, NB, NOMOM>(a);
 }
 
 template <int T, int RULE, int NB>
-static void launch_fused_rule_clip(const StepTable& tab, int64_t nvec, float mu, float omd, const float* clipf,
-                                   float* s_avg, float* h_avg, float* byz, float scale, int kind, double* partial,
-                                   int rule_f, float* defense, int* grid_io, hipStream_t s, bool nomom) {
-  if (nomom)
-    launch_fused_rule<T, RULE, NB, false, true>(tab, nvec, mu, omd, nullptr, s_avg, h_avg, byz, scale, kind, partial, rule_f, defense, grid_io, s);
-  else if (clipf != nullptr)
-    launch_fused_rule<T, RULE, NB, true>(tab, nvec, mu, omd, clipf, s_avg, h_avg, byz, scale, kind, partial, rule_f, defense, grid_io, s);
-  else
-    launch_fused_rule<T, RULE, NB, false>(tab, nvec, mu, omd, clipf, s_avg, h_avg, byz, scale, kind, partial, rule_f, defense, grid_io, s);
+static int launch_fused_rule_clip(const StepArgs& a) {
+  if (a.nomom) return launch_fused_rule<T, RULE, NB, false, true>(a);
+  return a.clipf != nullptr ? launch_fused_rule<T, RULE, NB, true>(a) : launch_fused_rule<T, RULE, NB, false>(a);
 }
 
 // instances: the two shapes of the reference's n = 25 runs (reproduce.py:165-209: f = 5 -> 20 honest rows + 5 Byzantine
@@ -879,34 +889,47 @@ static void launch_fused_rule_clip(const StepTable& tab, int64_t nvec, float mu,
 // instances of this kernel, two of the three minutes of the build.
 static bool fused_rule_shape(int h, int nb) { return (h == 20 && nb == 5) || (h == 14 && nb == 11); }
 static bool fused_rule_instance(int ks, int h, int nb, int op) {
-  if ((op != BM_OP_MEDIAN && op != BM_OP_TRMEAN && op != BM_OP_PHOCAS && op != BM_OP_MEAMED) || tuning().step_stream == 1 ||
-      ks != h)
-    return false;
-  return fused_rule_shape(h, nb);
+  return is_column_rule(op) && tuning().step_stream != 1 && ks == h && fused_rule_shape(h, nb);
 }
 
-static int launch_fused_rule_any(int op, int h, int nb, const StepTable& tab, int64_t nvec, float mu, float omd,
-                                 const float* clipf, float* s_avg, float* h_avg, float* byz, float scale, int kind,
-                                 double* partial, int rule_f, float* defense, int* grid_io, hipStream_t s,
-                                 bool nomom = false) {
-#define BM_FUSED_ARGS tab, nvec, mu, omd, clipf, s_avg, h_avg, byz, scale, kind, partial, rule_f, defense, grid_io, s, nomom
-#define BM_FUSED_CASE(TV, NBV)                                                  \
-  if (h == TV && nb == NBV) {                                                   \
-    if (op == BM_OP_MEDIAN)                                                     \
-      launch_fused_rule_clip<TV, BM_OP_MEDIAN, NBV>(BM_FUSED_ARGS);             \
-    else if (op == BM_OP_TRMEAN)                                                \
-      launch_fused_rule_clip<TV, BM_OP_TRMEAN, NBV>(BM_FUSED_ARGS);             \
-    else if (op == BM_OP_PHOCAS)                                                \
-      launch_fused_rule_clip<TV, BM_OP_PHOCAS, NBV>(BM_FUSED_ARGS);             \
-    else                                                                        \
-      launch_fused_rule_clip<TV, BM_OP_MEAMED, NBV>(BM_FUSED_ARGS);             \
-    BM_LAUNCH_CHECK();                                                          \
-    return 0;                                                                   \
+static int launch_fused_rule_any(int op, int nb, int rule_f, float* defense, StepArgs a) {
+  a.rule_f = rule_f;
+  a.defense = defense;
+#define BM_FUSED_CASE(TV, NBV)                                                                 \
+  if (a.h == TV && nb == NBV) {                                                                \
+    if (op == BM_OP_MEDIAN) return launch_fused_rule_clip<TV, BM_OP_MEDIAN, NBV>(a);           \
+    if (op == BM_OP_TRMEAN) return launch_fused_rule_clip<TV, BM_OP_TRMEAN, NBV>(a);           \
+    if (op == BM_OP_PHOCAS) return launch_fused_rule_clip<TV, BM_OP_PHOCAS, NBV>(a);           \
+    return launch_fused_rule_clip<TV, BM_OP_MEAMED, NBV>(a);                                   \
   }
   BM_FUSED_CASE(20, 5) BM_FUSED_CASE(14, 11)
 #undef BM_FUSED_CASE
-#undef BM_FUSED_ARGS
   return BM_EINVAL;
+}
+
+double* pairwise_gram_area(void* ws);  // pairwise.hip
+int* pairwise_arrival_counter(void* ws);
+int pairwise_from_gram_partials(const float* const* rows, int n_full, int nc, int blocks, int64_t d, double* sq_nxn,
+                                void* ws, hipStream_t s);
+
+// First pass + distance pass in one kernel, one workgroup per CU (a.h = 20 or 14 rows, 16-byte columns): the partial
+// Gram matrices go to the pair workspace.
+template <int TT>
+static int launch_momentum_gram_rows(const StepArgs& a, int cus, void* ws_pair) {
+  auto kernel = a.nomom ? momentum_gram_kernel<TT, false, true>
+                        : (a.clipf != nullptr ? momentum_gram_kernel<TT, true> : momentum_gram_kernel<TT, false>);
+  constexpr int lds = SgShape<TT>::kLds;
+  // (static: red and mred of the partials' epilogue, 96 B)
+  if (const int rc = lds_opt_in(reinterpret_cast<const void*>(kernel), lds, kSgWaves * (sizeof(double) + sizeof(float)))) return rc;
+  *a.grid_io = cus;
+  hipLaunchKernelGGL(kernel, dim3(cus), dim3(kStepBurstBlock), lds, a.s, a.tab, (uint32_t)a.nvec, a.mu, a.omd, a.clipf,
+                     a.s_avg, a.h_avg, a.byz, a.scale, a.kind, (unsigned)tuning().pair_dither, a.partial,
+                     pairwise_gram_area(ws_pair), pairwise_arrival_counter(ws_pair), tuning().step_stagger_us * 100);
+  BM_LAUNCH_CHECK();
+  return 0;
+}
+static int launch_momentum_gram(const StepArgs& a, int cus, void* ws_pair) {
+  return a.h == 20 ? launch_momentum_gram_rows<20>(a, cus, ws_pair) : launch_momentum_gram_rows<14>(a, cus, ws_pair);
 }
 
 // Gram contribution of the d mod 4 trailing columns (at most 3) of the fused distance pass: one more partial block,
@@ -939,23 +962,18 @@ static int momentum_stats_impl(const float* const* sampled, int ks, float* const
                                float* byz_out, float scale, int attack_kind, double* out6, void* ws, void* stream,
                                int rule_op, int rule_f, int nb, float* defense_out) {
   if (sampled == nullptr || buffers == nullptr || out6 == nullptr || ws == nullptr || h < 1 || ks < h ||
-      ks > BM_MAX_ROWS || d < 0 || ((attack_kind & ~BM_ATTACK_DIRECTION) != BM_ATTACK_EMPIRE && (attack_kind & ~BM_ATTACK_DIRECTION) != BM_ATTACK_LITTLE))
+      ks > BM_MAX_ROWS || d < 0 || !is_identical_attack(attack_kind))
     return BM_EINVAL;
-  if (rule_op >= 0 && ((rule_op != BM_OP_MEDIAN && rule_op != BM_OP_TRMEAN && rule_op != BM_OP_PHOCAS && rule_op != BM_OP_MEAMED) ||
-                       nb < 1 || h + nb > BM_MAX_ROWS || (attack_kind & BM_ATTACK_DIRECTION) != 0 ||
+  if (rule_op >= 0 && (!is_column_rule(rule_op) || nb < 1 || h + nb > BM_MAX_ROWS || (attack_kind & BM_ATTACK_DIRECTION) != 0 ||
                        (d > 0 && (byz_out == nullptr || defense_out == nullptr)) ||
                        (rule_op != BM_OP_MEDIAN && (rule_f < 0 || h + nb < 2 * rule_f + 1))))
     return BM_EINVAL;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  StepTable tab{};
-  for (int i = 0; i < ks; ++i) tab.g[i] = sampled[i];
-  for (int i = 0; i < h; ++i) tab.b[i] = buffers[i];
-  // pad the tables with their last row: the streaming kernel loads whole batches unconditionally
-  for (int i = ks; i < BM_MAX_ROWS; ++i) tab.g[i] = sampled[ks - 1];
-  for (int i = h; i < BM_MAX_ROWS; ++i) tab.b[i] = buffers[h - 1];
   const int vec = Alignment().of(sampled_avg).of(honest_avg).of(byz_out).of(rule_op >= 0 ? defense_out : nullptr)
                       .of(sampled, ks).of(buffers, h).vec();
   double* partial = static_cast<double*>(ws);
+  const StepArgs pass{make_step_table(sampled, ks, buffers, h), ks, h, 0, mu, one_minus_damp, clip_factors, sampled_avg,
+                      honest_avg, byz_out, scale, attack_kind, partial, nullptr, s};
   // pieces (byte offsets fit 32 bits inside the register-resident kernel) share the workspace: each leaves at most
   // cap + 1 partial sets, all of them at most kStepMaxBlocks + 1
   const int64_t pieces = piece_count(d);
@@ -966,24 +984,17 @@ static int momentum_stats_impl(const float* const* sampled, int ks, float* const
   const bool fusable = rule_op >= 0 && fused_rule_instance(ks, h, nb, rule_op);
   int nparts = 0;
   const int rc = for_pieces(d, [&](int64_t lo, int64_t dp) {
-    const StepTable piece = tab.advanced(lo);
-    float* sa = advanced(sampled_avg, lo);
-    float* ha = advanced(honest_avg, lo);
-    float* bz = advanced(byz_out, lo);
+    const StepArgs piece = pass.moved(lo);
     int64_t ruled = 0;  // columns of this piece the fused kernel covered
     const int rc = for_body_and_tail<4>(Tail::kOwnLaunch, vec, dp, kStepBlock, caps_of(cap), [&](auto width, Span& sp) {
       constexpr int VEC = decltype(width)::value;
-      double* part = partial + (int64_t)sp.part * 6;
       if constexpr (VEC == 4) {
         if (fusable) {
           ruled = sp.end;
-          return launch_fused_rule_any(rule_op, h, nb, piece, sp.count, mu, one_minus_damp, clip_factors, sa, ha, bz, scale,
-                                       attack_kind, part, rule_f, defense_out + lo, &sp.grid, s);
+          return launch_fused_rule_any(rule_op, nb, rule_f, defense_out + lo, piece.at(sp));
         }
       }
-      return dispatch_momentum_stats<VEC>(piece.advanced(sp.first), ks, h, sp.count, mu, one_minus_damp, clip_factors,
-                                          advanced(sa, sp.first), advanced(ha, sp.first), advanced(bz, sp.first), scale,
-                                          attack_kind, part, &sp.grid, s);
+      return dispatch_momentum_stats<VEC>(piece.at(sp));
     }, &nparts);
     if (rc != 0 || rule_op < 0 || ruled == dp) return rc;
     // the columns of this piece the fused kernel did not cover: the rule as its own launch
@@ -1018,13 +1029,6 @@ extern "C" int bm_momentum_stats_colwise(const float* const* sampled, int ks, fl
                                  byz_out, scale, attack_kind, out6, ws, stream, rule_op, rule_f, n_byz, defense_out);
 }
 
-namespace bm {
-double* pairwise_gram_area(void* ws);       // pairwise.hip
-int* pairwise_arrival_counter(void* ws);
-int pairwise_from_gram_partials(const float* const* rows, int n_full, int nc, int blocks, int64_t d, double* sq_nxn,
-                                void* ws, hipStream_t s);
-}
-
 extern "C" int bm_momentum_stats_sqdist(const float* const* sampled, int ks, float* const* buffers, int h, int64_t d,
                                         int64_t d_total, float mu, float one_minus_damp, const float* clip_factors,
                                         float* sampled_avg, float* honest_avg, float* byz_out, float scale,
@@ -1034,7 +1038,7 @@ extern "C" int bm_momentum_stats_sqdist(const float* const* sampled, int ks, flo
   const int n = h + n_byz;
   if (sampled == nullptr || buffers == nullptr || out6 == nullptr || ws == nullptr || ws_pair == nullptr ||
       sq_nxn == nullptr || h < 1 || ks < h || ks > BM_MAX_ROWS || n_byz < 1 || n > BM_MAX_ROWS || d < 0 || d_total < d ||
-      (attack_kind != BM_ATTACK_EMPIRE && attack_kind != BM_ATTACK_LITTLE) || (d > 0 && byz_out == nullptr))
+      !is_identical_attack(attack_kind) || (attack_kind & BM_ATTACK_DIRECTION) != 0 || (d > 0 && byz_out == nullptr))
     return BM_EINVAL;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const float* rows[BM_MAX_ROWS];
@@ -1045,58 +1049,32 @@ extern "C" int bm_momentum_stats_sqdist(const float* const* sampled, int ks, flo
   const bool shape_ok = ks == h && ((h == 20 && n_byz <= 6) || (h == 14 && n_byz == 11));  // n = 25 with f = 5 / 11, and neighbours
   const bool fused = shape_ok && vec == 4 && honest_avg != nullptr &&
                      d <= kMaxColsPerLaunch && tuning().step_stream != 1 && tuning().pair_mode == 0 &&
-                     tuning().pair_planes != 3 && tuning().step_burst > 0 &&
-                     d / 4 / ((int64_t)cus * kStepBurstBlock) >= tuning().step_burst;
+                     tuning().pair_planes != 3 && burst_ready(d / 4, cus);
   if (!fused) {  // the two passes one after the other: same results as the fused kernel up to the distances' rounding
     int rc = bm_momentum_stats(sampled, ks, buffers, h, d, mu, one_minus_damp, clip_factors, sampled_avg, honest_avg,
                                byz_out, scale, attack_kind, out6, ws, stream);
     if (rc != 0) return rc;
     return bm_pairwise_sqdist_shard(rows, n, d, d_total, sq_nxn, ws_pair, stream);
   }
-  StepTable tab{};
-  for (int i = 0; i < ks; ++i) tab.g[i] = sampled[i];
-  for (int i = 0; i < h; ++i) tab.b[i] = buffers[i];
-  for (int i = ks; i < BM_MAX_ROWS; ++i) tab.g[i] = sampled[ks - 1];
-  for (int i = h; i < BM_MAX_ROWS; ++i) tab.b[i] = buffers[h - 1];
   double* partial = static_cast<double*>(ws);
-  double* gram_partial = pairwise_gram_area(ws_pair);
+  const StepArgs pass{make_step_table(sampled, ks, buffers, h), ks, h, 0, mu, one_minus_damp, clip_factors, sampled_avg,
+                      honest_avg, byz_out, scale, attack_kind, partial, nullptr, s};
   const int nc = h + 1;  // rows of the compact Gram
   const int per_block = nc * (nc + 1) / 2;
-  void (*kern)(StepTable, uint32_t, float, float, const float*, float*, float*, float*, float, int, unsigned, double*,
-               double*, int*, int);
-  int lds;
-  if (h == 20) {
-    kern = clip_factors != nullptr ? momentum_gram_kernel<20, true> : momentum_gram_kernel<20, false>;
-    lds = SgShape<20>::kLds;
-  } else {
-    kern = clip_factors != nullptr ? momentum_gram_kernel<14, true> : momentum_gram_kernel<14, false>;
-    lds = SgShape<14>::kLds;
-  }
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  if (e != hipSuccess) return hip_code(e);
   int nparts = 0, blocks = 0;
   // body: one workgroup per CU; the at most 3 trailing columns: the scalar form of the first pass, and their Gram as one more block
   const int rc = for_body_and_tail<4>(Tail::kOwnLaunch, vec, d, kStepBlock, caps_of(kStepPieceCap), [&](auto width, Span& sp) {
     constexpr int VEC = decltype(width)::value;
     if constexpr (VEC == 4) {
-      sp.grid = cus;
-      hipLaunchKernelGGL(kern, dim3(cus), dim3(kStepBurstBlock), lds, s, tab, (uint32_t)sp.count, mu, one_minus_damp,
-                         clip_factors, sampled_avg, honest_avg, byz_out, scale, attack_kind, (unsigned)tuning().pair_dither,
-                         partial, gram_partial, pairwise_arrival_counter(ws_pair), tuning().step_stagger_us * 100);
-      BM_LAUNCH_CHECK();
       blocks = cus;
-      return 0;
+      return launch_momentum_gram(pass.at(sp), cus, ws_pair);
     } else if constexpr (VEC == 1) {
-      if (const int rc = dispatch_momentum_stats<1>(tab.advanced(sp.first), ks, h, sp.count, mu, one_minus_damp, clip_factors,
-                                                    advanced(sampled_avg, sp.first), honest_avg + sp.first,
-                                                    byz_out + sp.first, scale, attack_kind,
-                                                    partial + (int64_t)sp.part * 6, &sp.grid, s))
-        return rc;
+      if (const int rc = dispatch_momentum_stats<1>(pass.at(sp))) return rc;
       RowTable trows{};
       for (int i = 0; i < h; ++i) trows.p[i] = buffers[i] + sp.first;
       trows.p[h] = byz_out + sp.first;
       hipLaunchKernelGGL(tail_gram_kernel, dim3(1), dim3(256), 0, s, trows, nc, honest_avg + sp.first, (int)sp.count,
-                         gram_partial + (int64_t)blocks * per_block);
+                         pairwise_gram_area(ws_pair) + (int64_t)blocks * per_block);
       BM_LAUNCH_CHECK();
       blocks += 1;
       return 0;
@@ -1132,8 +1110,7 @@ extern "C" int bm_stack_stats_colwise(const float* const* rows, int k, int64_t d
   using namespace bm;
   const int n = k + n_byz;
   if (rows == nullptr || out6 == nullptr || ws == nullptr || k < 1 || n_byz < 1 || n > BM_MAX_ROWS || d < 0 ||
-      (attack_kind != BM_ATTACK_EMPIRE && attack_kind != BM_ATTACK_LITTLE) ||
-      (rule_op != BM_OP_MEDIAN && rule_op != BM_OP_TRMEAN && rule_op != BM_OP_PHOCAS && rule_op != BM_OP_MEAMED) ||
+      !is_identical_attack(attack_kind) || (attack_kind & BM_ATTACK_DIRECTION) != 0 || !is_column_rule(rule_op) ||
       (rule_op != BM_OP_MEDIAN && (rule_f < 0 || n < 2 * rule_f + 1)) ||
       (d > 0 && (avg_out == nullptr || byz_out == nullptr || defense_out == nullptr)))
     return BM_EINVAL;
@@ -1142,18 +1119,15 @@ extern "C" int bm_stack_stats_colwise(const float* const* rows, int k, int64_t d
   const bool fused = fused_rule_shape(k, n_byz) && vec == 4 && d % 4 == 0 && d > 0 && d <= kMaxColsPerLaunch &&
                      tuning().step_stream != 1;
   if (fused) {
-    StepTable tab{};
-    for (int i = 0; i < BM_MAX_ROWS; ++i) {
-      tab.g[i] = rows[i < k ? i : k - 1];
-      tab.b[i] = nullptr;  // never dereferenced without momentum
-    }
     double* partial = static_cast<double*>(ws);
+    StepArgs pass{make_step_table(rows, k, nullptr, k), k, k, 0, 0.0f, 1.0f, nullptr, nullptr, avg_out, byz_out, scale,
+                  attack_kind, partial, nullptr, s};
+    pass.nomom = true;
     int nparts = 0;
     // (d % 4 == 0: the body is the whole pass)
     const int rc = for_body_and_tail<4>(Tail::kOwnLaunch, vec, d, kStepBlock, caps_of(kStepPieceCap), [&](auto width, Span& sp) {
       if constexpr (decltype(width)::value == 4)
-        return launch_fused_rule_any(rule_op, k, n_byz, tab, sp.count, 0.0f, 1.0f, nullptr, nullptr, avg_out, byz_out, scale,
-                                     attack_kind, partial, rule_f, defense_out, &sp.grid, s, true);
+        return launch_fused_rule_any(rule_op, n_byz, rule_f, defense_out, pass.at(sp));
       else
         return BM_EINVAL;
     }, &nparts);
@@ -1177,7 +1151,7 @@ extern "C" int bm_stack_stats_sqdist(const float* const* rows, int k, int64_t d,
   const int n = k + n_byz;
   if (rows == nullptr || out6 == nullptr || ws == nullptr || ws_pair == nullptr || sq_nxn == nullptr || k < 1 ||
       n_byz < 1 || n > BM_MAX_ROWS || d < 0 || d_total < d ||
-      (attack_kind != BM_ATTACK_EMPIRE && attack_kind != BM_ATTACK_LITTLE) ||
+      !is_identical_attack(attack_kind) || (attack_kind & BM_ATTACK_DIRECTION) != 0 ||
       (d > 0 && (avg_out == nullptr || byz_out == nullptr)))
     return BM_EINVAL;
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1186,39 +1160,28 @@ extern "C" int bm_stack_stats_sqdist(const float* const* rows, int k, int64_t d,
   for (int i = k; i < n; ++i) all[i] = byz_out;
   const int vec = Alignment().of(avg_out).of(byz_out).of(rows, k).vec();
   const int cus = compute_units();
-  const int64_t nvec = d / 4;
   const bool fused = nomom_shape(k, n_byz) && vec == 4 && d % 4 == 0 && d <= kMaxColsPerLaunch &&
                      tuning().step_stream != 1 && tuning().pair_mode == 0 && tuning().pair_planes != 3 &&
-                     tuning().step_burst > 0 && nvec / ((int64_t)cus * kStepBurstBlock) >= tuning().step_burst;
+                     burst_ready(d / 4, cus);
   if (!fused) {
     int rc = stack_stats_plain(rows, k, d, avg_out, byz_out, scale, attack_kind, out6, ws, stream);
     if (rc != 0) return rc;
     return bm_pairwise_sqdist_shard(all, n, d, d_total, sq_nxn, ws_pair, stream);
   }
-  StepTable tab{};
-  for (int i = 0; i < BM_MAX_ROWS; ++i) {
-    tab.g[i] = rows[i < k ? i : k - 1];
-    tab.b[i] = nullptr;
-  }
   double* partial = static_cast<double*>(ws);
-  double* gram_partial = pairwise_gram_area(ws_pair);
-  void (*kern)(StepTable, uint32_t, float, float, const float*, float*, float*, float*, float, int, unsigned, double*,
-               double*, int*, int);
-  int lds;
-  if (k == 20) {
-    kern = momentum_gram_kernel<20, false, true>;
-    lds = SgShape<20>::kLds;
-  } else {
-    kern = momentum_gram_kernel<14, false, true>;
-    lds = SgShape<14>::kLds;
-  }
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  if (e != hipSuccess) return hip_code(e);
-  hipLaunchKernelGGL(kern, dim3(cus), dim3(kStepBurstBlock), lds, s, tab, (uint32_t)nvec, 0.0f, 1.0f, nullptr, nullptr,
-                     avg_out, byz_out, scale, attack_kind, (unsigned)tuning().pair_dither, partial, gram_partial,
-                     pairwise_arrival_counter(ws_pair), tuning().step_stagger_us * 100);
-  BM_LAUNCH_CHECK();
-  hipLaunchKernelGGL(step_finish_kernel, dim3(1), dim3(kFinishThreads), 0, s, partial, cus, out6);
+  StepArgs pass{make_step_table(rows, k, nullptr, k), k, k, 0, 0.0f, 1.0f, nullptr, nullptr, avg_out, byz_out, scale,
+                attack_kind, partial, nullptr, s};
+  pass.nomom = true;
+  int nparts = 0;
+  // (d % 4 == 0: the body is the whole pass)
+  const int rc = for_body_and_tail<4>(Tail::kOwnLaunch, vec, d, kStepBlock, caps_of(kStepPieceCap), [&](auto width, Span& sp) {
+    if constexpr (decltype(width)::value == 4)
+      return launch_momentum_gram(pass.at(sp), cus, ws_pair);
+    else
+      return BM_EINVAL;
+  }, &nparts);
+  if (rc != 0) return rc;
+  hipLaunchKernelGGL(step_finish_kernel, dim3(1), dim3(kFinishThreads), 0, s, partial, nparts, out6);
   BM_LAUNCH_CHECK();
   return pairwise_from_gram_partials(all, n, k + 1, cus, d, sq_nxn, ws_pair, s);
 }
