@@ -28,6 +28,17 @@ ENOCOMM, ECOMM = -100001, -100002
 OP_MEDIAN, OP_TRMEAN, OP_PHOCAS, OP_MEAMED = 0, 1, 2, 3
 WS_PAIRWISE, WS_AKSEL, WS_STATS, WS_DOT, WS_STEP, WS_STUDY = 0, 1, 2, 3, 4, 5
 STUDY_SLOTS = 32
+# where the scalars of a step are (step.py decodes both layouts into one record):
+# `out` of bm_study_stats ("out (DEVICE, BM_STUDY_SLOTS doubles)", include/bm_gar.h) ...
+STUDY_GRAM, STUDY_EX, STUDY_ATTACK = slice(0, 16), slice(16, 18), slice(18, 20)  # [4a+b] | <s,past> <s,C> | a2 ad
+STUDY_SUMS = slice(0, 20)     # the three above: what a sharded step adds over the ranks
+STUDY_MAXES = slice(20, 22)   # max|avg_a|, max|defense|
+STUDY_L2 = slice(22, 23)
+OUT3_SUMS, OUT3_MAX = slice(0, 2), slice(2, 3)  # bm_stack_stats: sum avg^2, sum_i |x_i - avg|^2 | max|avg|
+# ... and `stats_out` of bm_step_worker ("stats_out (DEVICE, bm_step_stats_count() doubles ...)", same header)
+STEP_S2, STEP_SD, STEP_H2, STEP_HD, STEP_D2, STEP_A2, STEP_AD, STEP_L2 = range(8)
+STEP_GRAM, STEP_EX = slice(8, 24), slice(24, 26)
+STEP_SMAX, STEP_HMAX, STEP_DMAX, STEP_AMAX = range(26, 30)
 RANK_KRUM, RANK_BULYAN = 0, 1
 ATTACK_EMPIRE, ATTACK_LITTLE, ATTACK_DIRECTION = 0, 1, 16
 

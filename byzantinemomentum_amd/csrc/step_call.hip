@@ -152,13 +152,12 @@ extern "C" int bm_step_worker(bm_comm* comm, const bm_step_params* p, const floa
 
   // ---- pass 1: momentum, statistics of the sampled and honest stacks, Byzantine vector; what the rule needs rides
   //      along: a coordinate-wise rule itself, or the distance pass of Krum / Bulyan (inside the same kernel at h = 20) ----
-  const bool distance_rule_ = p->rule == BM_RULE_KRUM || p->rule == BM_RULE_BULYAN;
   const bool rides_along = fr >= 1;  // the rule (or its distance pass) is fed from the first pass's registers
   const float* rows[BM_MAX_ROWS];
   for (int i = 0; i < h; ++i) rows[i] = buffers[i];
   for (int i = h; i < n; ++i) rows[i] = byz_out;
   const int m = p->m > 0 ? p->m : n - p->f_decl - 2;
-  if (rides_along && !distance_rule_) {
+  if (rides_along && !distance_rule) {
     const int op = p->rule == BM_RULE_MEDIAN ? BM_OP_MEDIAN
                    : p->rule == BM_RULE_TRMEAN ? BM_OP_TRMEAN : p->rule == BM_RULE_PHOCAS ? BM_OP_PHOCAS : BM_OP_MEAMED;
     rc = bm_momentum_stats_colwise(sampled, ks, buffers, h, d, p->mu, p->one_minus_damp, clipf, sampled_avg_out,
@@ -218,14 +217,10 @@ extern "C" int bm_step_worker(bm_comm* comm, const bm_step_params* p, const floa
   if (comm == nullptr) return 0;
   const int nranks = bm_comm_size(comm);
   if (nranks > BM_MAX_ROWS) return BM_EINVAL;
-  const double* gathered = sc->mine;
-  if (comm != nullptr) {
-    rc = bm_allgather_f32(comm, reinterpret_cast<const float*>(sc->mine), reinterpret_cast<float*>(sc->all),
-                          2 * kStatSlots, stream);  // doubles moved as pairs of 4-byte words
-    if (rc != 0) return rc;
-    gathered = sc->all;
-  }
-  hipLaunchKernelGGL(step_reduce_kernel, dim3(1), dim3(64), 0, s, gathered, comm != nullptr ? nranks : 1, stats_out);
+  rc = bm_allgather_f32(comm, reinterpret_cast<const float*>(sc->mine), reinterpret_cast<float*>(sc->all),
+                        2 * kStatSlots, stream);  // doubles moved as pairs of 4-byte words
+  if (rc != 0) return rc;
+  hipLaunchKernelGGL(step_reduce_kernel, dim3(1), dim3(64), 0, s, sc->all, nranks, stats_out);
   BM_LAUNCH_CHECK();
   return 0;
 }

@@ -109,6 +109,11 @@ class NativeComm:
 class HipBackend:
   """Compute legs on the local MI355X (libbm_gar.so).  No CPU fallback."""
 
+  # the optional legs step.AggregationStep plans with (read once, in its constructor); each names a method below
+  capabilities = frozenset((
+    "step_worker", "momentum_stats_colwise", "momentum_stats_sqdist", "stack_stats_colwise", "stack_stats_sqdist",
+    "device_search", "attack_ranking_device", "bulyan_pass2_eval", "order_pair", "colwise_eval", "sqdist2"))
+
   def __init__(self):
     from . import gars, stats
     self.gars = gars

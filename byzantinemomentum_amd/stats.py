@@ -22,6 +22,22 @@ __all__ = ["compute_avg_dev_max", "stack_stats_async", "study_dots", "study_stat
 _ptr = gars._ptr
 
 
+def _opt(t):
+  return _ptr(t) if t is not None else None
+
+
+def _require_scalar_on(t, device, message):  # a factor or a cursor handed over in DEVICE memory
+  if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == device and t.dtype == torch.float64
+          and t.numel() >= 1 and t.is_contiguous()):
+    raise gars.GarInputError(message)
+
+
+def _require_ext(ext, h):  # the squared distances among honests + [avg, avg + att] of the search's scalar forms
+  if not (isinstance(ext, torch.Tensor) and ext.is_cuda and ext.dtype == torch.float64 and ext.is_contiguous()
+          and tuple(ext.shape) == (h + 2, h + 2)):
+    raise gars.GarInputError(f"ext must be a contiguous float64 device tensor of shape ({h + 2}, {h + 2})")
+
+
 def _attack_id(attack, direction):
   kind = _lib.ATTACK_LITTLE if attack == "little" else _lib.ATTACK_EMPIRE
   return kind | (_lib.ATTACK_DIRECTION if direction else 0)
@@ -43,8 +59,7 @@ def stack_stats_async(samples, scale=None, attack="empire", want_avg=True, direc
   out3 = torch.empty(3, dtype=torch.float64, device=device)
   ws = gars._workspace(device, _lib.WS_STATS, k, d, "ws_stats")
   with torch.cuda.device(device):
-    _lib.check(lib.bm_stack_stats(_lib.pointer_table(samples), k, d, _ptr(avg) if avg is not None else None,
-                                  _ptr(scaled) if scaled is not None else None,
+    _lib.check(lib.bm_stack_stats(_lib.pointer_table(samples), k, d, _opt(avg), _opt(scaled),
                                   ctypes.c_float(scale if scale is not None else 0.0),
                                   _attack_id(attack, direction), _ptr(out3),
                                   _ptr(ws), gars._stream(device)), "bm_stack_stats")
@@ -108,8 +123,7 @@ def colwise_eval(rule, honests, copies, f, h_avg, direction, t):
   ws = gars._Scratch.get(device, "ws_eval", nbytes=int(lib.bm_colwise_eval_workspace_bytes()))
   with torch.cuda.device(device):
     if isinstance(t, torch.Tensor):
-      if not (t.is_cuda and t.device == device and t.dtype == torch.float64 and t.numel() >= 1 and t.is_contiguous()):
-        raise gars.GarInputError("colwise_eval: a tensor t must be a contiguous float64 tensor on the vectors' device")
+      _require_scalar_on(t, device, "colwise_eval: a tensor t must be a contiguous float64 tensor on the vectors' device")
       _lib.check(lib.bm_colwise_eval_tdev(_EVAL_OPS[rule], _lib.pointer_table(honests), h, copies, d, f, _ptr(h_avg),
                                           _ptr(direction), _ptr(t), _ptr(out), _ptr(ws), gars._stream(device)),
                  "bm_colwise_eval_tdev")
@@ -150,14 +164,12 @@ def bulyan_pass2_eval(honests, copies, order, f, m, h_avg, direction, t):
   ws = gars._Scratch.get(device, "ws_eval", nbytes=int(lib.bm_colwise_eval_workspace_bytes()))
   t_dev = None
   if isinstance(t, torch.Tensor):
-    if not (t.is_cuda and t.device == device and t.dtype == torch.float64 and t.numel() >= 1 and t.is_contiguous()):
-      raise gars.GarInputError("bulyan_pass2_eval: a tensor t must be a contiguous float64 tensor on the vectors' device")
+    _require_scalar_on(t, device, "bulyan_pass2_eval: a tensor t must be a contiguous float64 tensor on the vectors' device")
     t_dev, t = t, 0.0
   with torch.cuda.device(device):
     _lib.check(lib.bm_bulyan_pass2_eval(_lib.pointer_table(honests), h, int(copies), _ptr(order), int(f), int(m), d,
-                                        _ptr(h_avg), _ptr(direction), ctypes.c_float(float(t)),
-                                        _ptr(t_dev) if t_dev is not None else None, _ptr(out), _ptr(ws),
-                                        gars._stream(device)), "bm_bulyan_pass2_eval")
+                                        _ptr(h_avg), _ptr(direction), ctypes.c_float(float(t)), _opt(t_dev), _ptr(out),
+                                        _ptr(ws), gars._stream(device)), "bm_bulyan_pass2_eval")
   return out
 
 
@@ -204,7 +216,7 @@ class DeviceSearch:
     lib = _lib.load()
     self._keep = y  # (alive until the kernel that reads it has been queued behind its producer)
     with torch.cuda.device(self.device):
-      _lib.check(lib.bm_search_device_next(_ptr(self.state), _ptr(y) if y is not None else None, 1 if self.negative else 0,
+      _lib.check(lib.bm_search_device_next(_ptr(self.state), _opt(y), 1 if self.negative else 0,
                                            1 if last else 0, *self.shape, _ptr(self.t) if not last else None,
                                            _ptr(self.out), gars._stream(self.device)), "bm_search_device_next")
 
@@ -241,12 +253,11 @@ def study_stats(s_avg, h_avg, defense, byz, f_real, past_newest=None, curv=None,
   lib = _lib.load()
   out = torch.empty(_lib.STUDY_SLOTS, dtype=torch.float64, device=device)
   ws = gars._workspace(device, _lib.WS_STUDY, 1, d, "ws_study")
-  opt = lambda t: _ptr(t) if t is not None else None  # noqa: E731
   with torch.cuda.device(device):
-    _lib.check(lib.bm_study_stats_update(_ptr(s_avg), _ptr(h_avg), _ptr(defense), opt(byz if f_real > 0 else None),
-                                         int(f_real), opt(attack_avg_out), opt(past_newest), opt(curv), opt(past_oldest),
-                                         int(curv_mode), ctypes.c_float(mu), ctypes.c_float(oldest_weight), opt(params),
-                                         opt(origin), opt(update_momentum), ctypes.c_float(update_mu),
+    _lib.check(lib.bm_study_stats_update(_ptr(s_avg), _ptr(h_avg), _ptr(defense), _opt(byz if f_real > 0 else None),
+                                         int(f_real), _opt(attack_avg_out), _opt(past_newest), _opt(curv), _opt(past_oldest),
+                                         int(curv_mode), ctypes.c_float(mu), ctypes.c_float(oldest_weight), _opt(params),
+                                         _opt(origin), _opt(update_momentum), ctypes.c_float(update_mu),
                                          ctypes.c_float(update_omd), d, _ptr(out), _ptr(ws), gars._stream(device)),
                "bm_study_stats_update")
   if update_momentum is not None:
@@ -290,8 +301,7 @@ def momentum_stats(sampled, buffers, mu, one_minus_damp, clip_factors_dev=None, 
   [sum avg_s^2, sum_i |s_i-avg_s|^2, max|avg_s|, sum avg_h^2, sum_i |b_i-avg_h|^2, max|avg_h|]. No sync.
   """
   ks, d, device = gars._validate(list(sampled))
-  h, _, _ = gars._validate(list(buffers) + [sampled[0]])
-  h -= 1
+  h = gars._validate(list(buffers) + [sampled[0]])[0] - 1
   if h < 1 or ks < h:
     raise gars.GarInputError("momentum_stats needs 1 <= len(buffers) <= len(sampled)")
   lib = _lib.load()
@@ -304,15 +314,11 @@ def momentum_stats(sampled, buffers, mu, one_minus_damp, clip_factors_dev=None, 
   with torch.cuda.device(device):
     _lib.check(lib.bm_momentum_stats(
       _lib.pointer_table(sampled), ks, _lib.pointer_table(buffers), h, d, ctypes.c_float(mu),
-      ctypes.c_float(one_minus_damp), _ptr(clip_factors_dev) if clip_factors_dev is not None else None,
-      _ptr(s_avg), _ptr(h_avg), _ptr(byz) if byz is not None else None,
+      ctypes.c_float(one_minus_damp), _opt(clip_factors_dev), _ptr(s_avg), _ptr(h_avg), _opt(byz),
       ctypes.c_float(attack_scale if attack_scale is not None else 0.0),
       _attack_id(attack, direction), _ptr(out6), _ptr(ws),
       gars._stream(device)), "bm_momentum_stats")
   return s_avg, h_avg, byz, out6
-
-
-_COLWISE_OPS = {"median": _lib.OP_MEDIAN, "trmean": _lib.OP_TRMEAN, "phocas": _lib.OP_PHOCAS, "meamed": _lib.OP_MEAMED}
 
 
 def momentum_stats_colwise(sampled, buffers, mu, one_minus_damp, clip_factors_dev, attack_scale, attack, rule, f, n_byz):
@@ -331,9 +337,9 @@ def momentum_stats_colwise(sampled, buffers, mu, one_minus_damp, clip_factors_de
   with torch.cuda.device(device):
     _lib.check(lib.bm_momentum_stats_colwise(
       _lib.pointer_table(sampled), ks, _lib.pointer_table(buffers), h, d, ctypes.c_float(mu),
-      ctypes.c_float(one_minus_damp), _ptr(clip_factors_dev) if clip_factors_dev is not None else None,
+      ctypes.c_float(one_minus_damp), _opt(clip_factors_dev),
       _ptr(s_avg), _ptr(h_avg), _ptr(byz), ctypes.c_float(attack_scale), _attack_id(attack, False),
-      _COLWISE_OPS[rule], int(f), int(n_byz), _ptr(defense), _ptr(out6), _ptr(ws), gars._stream(device)),
+      _EVAL_OPS[rule], int(f), int(n_byz), _ptr(defense), _ptr(out6), _ptr(ws), gars._stream(device)),
       "bm_momentum_stats_colwise")
   return s_avg, h_avg, byz, defense, out6
 
@@ -358,8 +364,7 @@ def momentum_stats_sqdist(sampled, buffers, mu, one_minus_damp, clip_factors_dev
   with torch.cuda.device(device):
     _lib.check(lib.bm_momentum_stats_sqdist(
       _lib.pointer_table(sampled), ks, _lib.pointer_table(buffers), h, d, d if d_total is None else int(d_total),
-      ctypes.c_float(mu), ctypes.c_float(one_minus_damp),
-      _ptr(clip_factors_dev) if clip_factors_dev is not None else None, _ptr(s_avg), _ptr(h_avg), _ptr(byz),
+      ctypes.c_float(mu), ctypes.c_float(one_minus_damp), _opt(clip_factors_dev), _ptr(s_avg), _ptr(h_avg), _ptr(byz),
       ctypes.c_float(attack_scale), _attack_id(attack, False), int(n_byz), _ptr(sq), _ptr(out6), _ptr(ws), _ptr(ws_pair),
       gars._stream(device)), "bm_momentum_stats_sqdist")
   return s_avg, h_avg, byz, sq, out6
@@ -378,7 +383,7 @@ def stack_stats_colwise(rows, attack_scale, attack, rule, f, n_byz):
   ws = gars._workspace(device, _lib.WS_STEP, 1, d, "ws_step")
   with torch.cuda.device(device):
     _lib.check(lib.bm_stack_stats_colwise(_lib.pointer_table(rows), k, d, _ptr(avg), _ptr(byz),
-                                          ctypes.c_float(attack_scale), _attack_id(attack, False), _COLWISE_OPS[rule],
+                                          ctypes.c_float(attack_scale), _attack_id(attack, False), _EVAL_OPS[rule],
                                           int(f), int(n_byz), _ptr(defense), _ptr(out6), _ptr(ws),
                                           gars._stream(device)), "bm_stack_stats_colwise")
   return avg, byz, defense, out6
@@ -418,11 +423,10 @@ def multi_fma3(outs, ps, qs, a, b, p_scale_dev=None):
     raise gars.GarInputError("multi_fma3 needs as many p and q as out vectors")
   lib = _lib.load()
   gars.invalidate_rank_cache()
-  scale = _ptr(p_scale_dev) if p_scale_dev is not None else None
+  scale = _opt(p_scale_dev)
   with torch.cuda.device(device):
     if isinstance(b, torch.Tensor):
-      if not (b.is_cuda and b.device == device and b.dtype == torch.float64 and b.numel() >= 1 and b.is_contiguous()):
-        raise gars.GarInputError("multi_fma3: a tensor b must be a contiguous float64 tensor on the vectors' device")
+      _require_scalar_on(b, device, "multi_fma3: a tensor b must be a contiguous float64 tensor on the vectors' device")
       _lib.check(lib.bm_multi_fma3_bdev(_lib.pointer_table(outs), _lib.pointer_table(ps), _lib.pointer_table(qs), k, d,
                                         ctypes.c_float(a), _ptr(b), scale, gars._stream(device)), "bm_multi_fma3_bdev")
     else:
@@ -440,9 +444,7 @@ def attack_search_device(ext, h, k, f, rule, evals=16, negative=False, m=None):
   linesearch.attack_line_search.  Nothing is copied or awaited: hand `out[:1]` to multi_fma3 as b."""
   if rule not in DEVICE_SEARCH_RULES:
     raise ValueError(f"no device form of the search for rule {rule!r}")
-  if not (isinstance(ext, torch.Tensor) and ext.is_cuda and ext.dtype == torch.float64 and ext.is_contiguous()
-          and tuple(ext.shape) == (h + 2, h + 2)):
-    raise gars.GarInputError(f"ext must be a contiguous float64 device tensor of shape ({h + 2}, {h + 2})")
+  _require_ext(ext, h)
   if not isinstance(evals, int) or evals < 1:
     _lib.check(_lib.EINVAL, "attack_search_device (evals must be a positive integer)")
   lib = _lib.load()
@@ -461,12 +463,8 @@ def attack_ranking_device(ext, h, k, f, mode, t_dev, m=None):
   """linesearch.attack_ranking on the device (bm_attack_ranking_device): the ranking of honests + [avg + t*att] * k as a
   device int32[64] tensor (the n rows by rank, then zeros) from the DEVICE (h+2) x (h+2) matrix and a factor in DEVICE
   memory (float64[1]) — what bm_bulyan_pass2 / bm_bulyan_pass2_eval take as `order`.  Nothing is copied or awaited."""
-  if not (isinstance(ext, torch.Tensor) and ext.is_cuda and ext.dtype == torch.float64 and ext.is_contiguous()
-          and tuple(ext.shape) == (h + 2, h + 2)):
-    raise gars.GarInputError(f"ext must be a contiguous float64 device tensor of shape ({h + 2}, {h + 2})")
-  if not (isinstance(t_dev, torch.Tensor) and t_dev.is_cuda and t_dev.device == ext.device and t_dev.dtype == torch.float64
-          and t_dev.numel() >= 1 and t_dev.is_contiguous()):
-    raise gars.GarInputError("attack_ranking_device: the factor must be a contiguous float64 tensor on the matrix's device")
+  _require_ext(ext, h)
+  _require_scalar_on(t_dev, ext.device, "attack_ranking_device: the factor must be a contiguous float64 tensor on the matrix's device")
   lib = _lib.load()
   order = torch.empty(_lib.MAX_ROWS, dtype=torch.int32, device=ext.device)
   mode_id = {"krum": _lib.RANK_KRUM, "bulyan": _lib.RANK_BULYAN}[mode]
@@ -538,13 +536,12 @@ def step_worker(comm, sampled, buffers, n, f_decl, f_real, rule, m, mu, one_minu
                         past_count=past_count, attack_scale=attack_scale, mu=mu, one_minus_damp=one_minus_damp,
                         clip=clip if clip is not None else 0.0,
                         oldest_weight=-(mu ** (nb_past - 1)) if nb_past > 0 else 0.0)
-  opt = lambda t: _ptr(t) if t is not None else None  # noqa: E731
   gars.invalidate_rank_cache()
   with torch.cuda.device(device):
     _lib.check(lib.bm_step_worker(comm.handle if comm is not None else None, ctypes.byref(par),
                                   _lib.pointer_table(sampled), _lib.pointer_table(buffers), d,
                                   int(d_total) if d_total is not None else d, _ptr(defense),
-                                  _ptr(s_avg), _ptr(h_avg), opt(byz), None, opt(past_newest), opt(curv),
-                                  opt(past_oldest), opt(params), opt(origin), _ptr(stats), _ptr(ws),
+                                  _ptr(s_avg), _ptr(h_avg), _opt(byz), None, _opt(past_newest), _opt(curv),
+                                  _opt(past_oldest), _opt(params), _opt(origin), _ptr(stats), _ptr(ws),
                                   gars._stream(device)), "bm_step_worker")
   return defense, s_avg, h_avg, byz, stats

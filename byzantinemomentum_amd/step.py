@@ -28,14 +28,37 @@ synchronisation per evaluation, or ONE for the whole search when the rule is kru
 
 import collections
 import math
+from typing import NamedTuple, Optional
 
 import torch
+
+from . import _lib, linesearch
 
 __all__ = ["AggregationStep"]
 
 _RULES = ("krum", "bulyan", "median", "trmean", "phocas", "meamed", "aksel", "brute", "average", "cge")
-_NEEDS_F = {"krum", "bulyan", "trmean", "phocas", "meamed", "aksel", "brute", "cge"}
+_COLWISE = ("median", "trmean", "phocas", "meamed")
+_DISTANCE = ("krum", "bulyan")
 MAX_PAST = 4096  # past sampled averages kept for the curvature term (each is one d-vector of device memory)
+
+
+class StepPlan(NamedTuple):
+  """The forms a step takes, decided ONCE from the constructor's arguments and the backend's `capabilities`
+  (AggregationStep._make_plan).  run() and _search_factor() read it; they add three run-time facts only, each where it
+  matters: ks == h (update placement), whether the vectors are on a GPU, and d (bulyan_pass2_eval_supported)."""
+  only_m: bool            # no argument of the rule but "m"
+  analytic: bool          # line_search "auto" / "host": the search may use a rule's special form
+  first_pass: str         # "rule" / "sqdist": the coordinate-wise rule / the distance pass of Krum, Bulyan rides along;
+                          # "plain"; "direction": a factor search follows, the first pass forms the attack direction only
+  search: Optional[str]   # None (fixed factor), "scalar_device", "scalar_host", "bulyan", "median", "colwise_eval", "generic"
+  device_cursor: bool     # the exploration's cursor (for Bulyan, the ranking too) lives in device memory
+  single_call: bool       # run() is one bm_step_worker call
+  capabilities: frozenset  # the optional legs the backend declared
+
+
+# every scalar of the study row, from the packed vector of bm_step_worker or from the exchange of the sequence
+# (gram: 4 x 4, row-major, of sampled avg, honest avg, defense, attack avg; ex0 / ex1: <s, newest past>, <s, C>)
+_StudyRecord = collections.namedtuple("_StudyRecord", "s2 sd smax h2 hd hmax a2 ad amax d2 dmax l2 gram ex0 ex1 prev_s2")
 
 
 class AggregationStep:
@@ -104,11 +127,47 @@ class AggregationStep:
     self._pending = None
     self._update = None
     self._prev_stats = None    # single-call form: the previous step's reduced statistics (slot 0 = ||avg_s||^2)
-    extra_args = set(self.gar_args) - {"m"}
-    self.single_call = bool(single_call and attack_evals is None and momentum_at == "worker"
-                            and hasattr(self.ops, "step_worker")
-                            and gar in ("krum", "bulyan", "median", "trmean", "phocas", "meamed") and not extra_args
-                            and (not self.agg.collective or self.agg.native is not None))
+    self.plan = self._make_plan(single_call)
+    self.single_call = self.plan.single_call
+
+  def _make_plan(self, single_call):
+    """Every decision that depends on the constructor's arguments and the backend alone.  A backend names its optional
+    legs in a `capabilities` set (sharded.HipBackend); one that declares none gets the plain first pass, the host's
+    cursor and the forms of the search that need the common legs only."""
+    caps = frozenset(getattr(self.ops, "capabilities", ()))
+    gar, k, fixed = self.gar, self.f_real, self.attack_evals is None
+    only_m = not (set(self.gar_args) - {"m"})
+    analytic = self.line_search in ("auto", "host")
+    # the first pass: momentum_stats* (worker placement) and stack_stats* (update placement) make the same choice
+    stem = {"worker": "momentum_stats_", "update": "stack_stats_"}.get(self.momentum_at)
+    if not fixed:
+      first_pass = "direction"
+    elif stem and k >= 1 and not self.gar_args and gar in _COLWISE and stem + "colwise" in caps:
+      first_pass = "rule"
+    elif stem and k >= 1 and only_m and gar in _DISTANCE and stem + "sqdist" in caps:
+      first_pass = "sqdist"
+    else:
+      first_pass = "plain"
+    # the factor search; Brute keeps the host's cursor (its checked call synchronises per evaluation anyway), Bulyan
+    # moves cursor and ranking to the device together
+    small = self.h + 2 <= 64  # the (h+2) x (h+2) matrix of the scalar forms fits the kernels' 64 rows
+    device_cursor = self.line_search == "auto" and "device_search" in caps and gar != "brute"
+    if fixed:
+      search, device_cursor = None, False
+    elif analytic and gar in linesearch.ANALYTIC_RULES and small and only_m:
+      device_cursor = self.line_search == "auto" and gar in getattr(self.ops, "device_search_rules", ())
+      search = "scalar_device" if device_cursor else "scalar_host"
+    elif analytic and gar == "bulyan" and k >= 1 and small and only_m:
+      search, device_cursor = "bulyan", device_cursor and "attack_ranking_device" in caps
+    elif analytic and gar == "median" and k >= 1:
+      search = "median"
+    elif analytic and gar in _COLWISE and k >= 1 and not self.gar_args and "colwise_eval" in caps:
+      search = "colwise_eval"
+    else:
+      search = "generic"
+    single = bool(single_call and fixed and self.momentum_at == "worker" and "step_worker" in caps
+                  and gar in _DISTANCE + _COLWISE and only_m and (not self.agg.collective or self.agg.native is not None))
+    return StepPlan(only_m, analytic, first_pass, search, device_cursor, single, caps)
 
   # ------------------------------------------------------------------------ #
 
@@ -179,116 +238,130 @@ class AggregationStep:
   def _search_factor(self, honests, h_avg, direction):
     """attacks/identical.py:67-77: the factor maximising |GAR(honests + [avg + t*dir]*f_real) - avg|^2 under
     the evaluation budget.  Like the reference, `negative` flips the sign of the candidates DURING the
-    search only; the factor returned (and then applied) is the positive abscissa the search settled on."""
-    from . import linesearch
-    ops, agg, h, k = self.ops, self.agg, self.h, self.f_real
-    if self.line_search in ("auto", "host") and self.gar in linesearch.ANALYTIC_RULES and h + 2 <= 64 and \
-       not (set(self.gar_args) - {"m"}):
-      unit = torch.empty_like(h_avg)
-      ops.multi_fma3([unit], [h_avg], [direction], 1.0, 1.0)   # avg + dir: the candidate of factor 1
-      sq = agg.global_sqdist(list(honests) + [h_avg, unit])
-      if self.line_search == "auto" and self.gar in getattr(ops, "device_search_rules", ()):
-        # every candidate evaluated where the distances are: no copy, no synchronisation; the factor stays on the
-        # device (a tensor: multi_fma3 reads it there) and last_factor / last_search fetch it when asked
-        found = ops.attack_search_device(sq, h, k, self.f_decl, self.gar, evals=self.attack_evals,
-                                         negative=self.attack_negative, m=self.gar_args.get("m"))
-        self.last_search = found
-        return found
-      ext = self._fetch(sq)  # the search's only synchronisation
-      factor, self.last_search = linesearch.attack_line_search(
-        ext, h, k, self.f_decl, self.gar, evals=self.attack_evals, negative=self.attack_negative,
-        m=self.gar_args.get("m"))
-      return factor
+    search only; the factor returned (and then applied) is the positive abscissa the search settled on.
+    Returns a number, or the device tensor whose [0] is the factor; sets last_search."""
+    plan = self.plan
+    if plan.search in ("scalar_device", "scalar_host"):
+      return self._search_scalar(honests, h_avg, direction)
+    on_device = plan.device_cursor and h_avg.is_cuda
+    form = {"bulyan": self._bulyan_objective, "median": self._median_objective,
+            "colwise_eval": self._colwise_objective, "generic": self._generic_objective}[plan.search]
+    return self._drive(form(honests, h_avg, direction, on_device), h_avg, on_device)
 
-    rule = lambda cand, t: self._aggregate(list(honests) + [cand] * k)  # noqa: E731
-    n = h + k
-    bulyan_objective = None
-    host_ranked = self.gar == "brute"  # (its checked call reads a status: a synchronisation per evaluation anyway)
-    if self.line_search in ("auto", "host") and self.gar == "bulyan" and k >= 1 and h + 2 <= 64 and hasattr(ops, "bulyan_pass2") \
-       and not (set(self.gar_args) - {"m"}):
-      # Bulyan's second pass needs the vectors, its ranking does not: the distances among honests + [avg + t*dir] * k
-      # are functions of the inner products of ONE distance pass over honests + [avg, avg + dir] (as for krum above),
-      # so every candidate is ranked on the host and costs pass 2 alone (m + 1 row passes instead of n + m + 1)
-      m = self.gar_args.get("m") or n - self.f_decl - 2
-      unit = torch.empty_like(h_avg)
-      ops.multi_fma3([unit], [h_avg], [direction], 1.0, 1.0)
-      sq_dev = agg.global_sqdist(list(honests) + [h_avg, unit])
-      # ranked where the matrix is, from the factor the device cursor left there (bm_attack_ranking_device: no copy, no
-      # synchronisation) — or on the host from the number the host's cursor proposed (one copy of the matrix per search)
-      device_ranked = self.line_search == "auto" and hasattr(ops, "attack_ranking_device") and sq_dev.is_cuda
-      ext = None if device_ranked else self._fetch(sq_dev)
-      host_ranked = not device_ranked
-
-      def ranking(t):
-        if isinstance(t, torch.Tensor):
-          return ops.attack_ranking_device(sq_dev, h, k, self.f_decl, "bulyan", t, m)
-        order = linesearch.attack_ranking(ext, h, k, self.f_decl, "bulyan", t, m)
-        return ops.index_tensor(order + [0] * (64 - n), h_avg)
-
-      def rule(cand, t):  # noqa: F811
-        return ops.bulyan_pass2(list(honests) + [cand] * k, ranking(t), self.f_decl, m)
-
-      if hasattr(ops, "bulyan_pass2_eval") and ops.bulyan_pass2_eval_supported(n, self.f_decl, m, h_avg.shape[0]):
-        # ... and pass 2 has an evaluate-only form for the shapes of the reference's experiments: the candidate in
-        # registers, the objective accumulated in the same kernel, nothing written (bm_bulyan_pass2_eval)
-        def bulyan_objective(t):
-          return ops.bulyan_pass2_eval(honests, k, ranking(t), self.f_decl, m, h_avg, direction, t)
-    if self.line_search in ("auto", "host") and self.gar == "median" and k >= 1:
-      # The lower median of the h honest values and k copies of ONE value b is monotone in b, equals b while b lies
-      # between two order statistics of the honest values and stays at them outside: median(honests + [b] * k) =
-      # middle of (b, lo, hi) per coordinate, with lo / hi the medians of the honest values and k copies of -inf /
-      # +inf.  Two passes over the honest rows for the whole search, then every candidate is the median of THREE
-      # rows (4 row passes instead of n + 1): the same value of the rule at every coordinate — it returns one of its
-      # inputs, no arithmetic — hence the same objective, bit for bit, as evaluating the rule on the n rows.
-      if hasattr(ops, "order_pair") and ops.order_pair_supported(h):
-        lo, hi = ops.order_pair(honests, (n - 1) // 2 - k, (n - 1) // 2)   # both in one pass over the honest rows
-      else:
-        lo = agg.median(list(honests) + [torch.full_like(h_avg, -math.inf)] * k)
-        hi = agg.median(list(honests) + [torch.full_like(h_avg, math.inf)] * k)
-      rule = lambda cand, t: agg.median([cand, lo, hi])  # noqa: E731
-
-    fused_eval = (self.line_search in ("auto", "host") and k >= 1 and not self.gar_args and hasattr(ops, "colwise_eval")
-                  and ops.colwise_eval_supported(self.gar, n))
-    eval_rows, eval_copies, eval_f = honests, k, self.f_decl
-    if (self.line_search in ("auto", "host") and self.gar == "median" and k >= 1 and hasattr(ops, "colwise_eval")
-        and ops.colwise_eval_supported("median", 3)):
-      # ... and the middle of (lo, hi, candidate) has an evaluate-only instance: 4 row passes, nothing written
-      fused_eval, eval_rows, eval_copies, eval_f = True, [lo, hi], 1, 0
-
-    def evaluate(t):
-      """The objective of candidate t as a device fp64[1] tensor; t a number or the device cursor's tensor."""
-      if bulyan_objective is not None:
-        sq = bulyan_objective(t)
-      elif fused_eval:
-        # trmean / phocas / meamed: candidate, rule and objective in ONE pass over the honest rows, nothing written
-        # (bm_colwise_eval: h + 2 row passes instead of h + 5 read and 2 written); the same value at every column
-        sq = ops.colwise_eval(self.gar, eval_rows, eval_copies, eval_f, h_avg, direction, t)
-      else:
-        cand = torch.empty_like(h_avg)
-        ops.multi_fma3([cand], [h_avg], [direction], 1.0, t)
-        out = rule(cand, t)
-        # aggregated.sub_(grad_avg); dot with itself: one pass over the two vectors where the backend has it
-        sq = ops.sqdist2(out, h_avg) if hasattr(ops, "sqdist2") else ops.pairwise_sqdist([out, h_avg])[0, 1].reshape(1)
-      agg.all_reduce_sum(sq)
+  def _drive(self, evaluate, h_avg, on_device):
+    """Run `evaluate(t) -> device fp64[1]` under the exploration of tools.line_maximize, its cursor in device memory
+    or on the host."""
+    def objective(t):
+      sq = evaluate(t)
+      self.agg.all_reduce_sum(sq)
       return sq
 
-    if self.line_search == "auto" and not host_ranked and hasattr(ops, "device_search") and h_avg.is_cuda:
-      # the cursor of the exploration in device memory: every evaluation reads its factor there and leaves its objective
-      # there — the host queues the whole search and waits for none of it (Bulyan's candidates are ranked by one
-      # workgroup from that factor; Brute's checked call synchronises by itself and keeps the host's cursor)
-      cursor = ops.device_search(h_avg.device, self.attack_evals, self.attack_negative)
+    if on_device:
+      # every evaluation reads its factor in device memory and leaves its objective there: the host queues the whole
+      # search and waits for none of it; last_factor / last_search fetch the result when asked
+      cursor = self.ops.device_search(h_avg.device, self.attack_evals, self.attack_negative)
       y = None
       for _ in range(self.attack_evals):
-        y = evaluate(cursor.next(y))
-      found = cursor.finish(y)
-      self.last_search = found
+        y = objective(cursor.next(y))
+      found = self.last_search = cursor.finish(y)  # (not read back through the property: that would fetch it)
       return found
-
-    def scape(x):
-      return evaluate(-x if self.attack_negative else x).item()
-
-    factor, self.last_search = linesearch.line_maximize(scape, evals=self.attack_evals)
+    factor, self.last_search = linesearch.line_maximize(
+      lambda x: objective(-x if self.attack_negative else x).item(), evals=self.attack_evals)
     return factor
+
+  def _unit_sqdist(self, honests, h_avg, direction):
+    """The (h+2) x (h+2) squared distances among honests + [avg, avg + dir]: every distance of a candidate stack is a
+    function of these inner products, so ONE distance pass serves a whole search."""
+    unit = torch.empty_like(h_avg)
+    self.ops.multi_fma3([unit], [h_avg], [direction], 1.0, 1.0)   # avg + dir: the candidate of factor 1
+    return self.agg.global_sqdist(list(honests) + [h_avg, unit])
+
+  def _search_scalar(self, honests, h_avg, direction):
+    """krum / brute / average: every evaluation is a function of the scalars of one distance pass (linesearch.py)."""
+    sq = self._unit_sqdist(honests, h_avg, direction)
+    args = dict(evals=self.attack_evals, negative=self.attack_negative, m=self.gar_args.get("m"))
+    if self.plan.search == "scalar_device":
+      # evaluated where the distances are: no copy, no synchronisation; the factor stays on the device (a tensor:
+      # multi_fma3 reads it there)
+      found = self.last_search = self.ops.attack_search_device(sq, self.h, self.f_real, self.f_decl, self.gar, **args)
+      return found
+    ext = self._fetch(sq)  # the search's only synchronisation
+    factor, self.last_search = linesearch.attack_line_search(ext, self.h, self.f_real, self.f_decl, self.gar, **args)
+    return factor
+
+  def _written_objective(self, rule, h_avg, direction):
+    """evaluate(t) that writes the candidate, runs `rule(cand, t)` on it and measures the output against the average."""
+    ops = self.ops
+
+    def evaluate(t):
+      cand = torch.empty_like(h_avg)
+      ops.multi_fma3([cand], [h_avg], [direction], 1.0, t)
+      out = rule(cand, t)
+      # aggregated.sub_(grad_avg); dot with itself: one pass over the two vectors where the backend has it
+      if "sqdist2" in self.plan.capabilities:
+        return ops.sqdist2(out, h_avg)
+      return ops.pairwise_sqdist([out, h_avg])[0, 1].reshape(1)
+    return evaluate
+
+  def _generic_objective(self, honests, h_avg, direction, on_device=False):
+    """The rule itself on the n rows, once per evaluation, like the reference."""
+    return self._written_objective(lambda cand, t: self._aggregate(list(honests) + [cand] * self.f_real), h_avg, direction)
+
+  def _colwise_objective(self, honests, h_avg, direction, on_device=False):
+    """trmean / phocas / meamed: candidate, rule and objective in ONE pass over the honest rows, nothing written
+    (bm_colwise_eval: h + 2 row passes instead of h + 5 read and 2 written); the same value at every column."""
+    ops, k = self.ops, self.f_real
+    if not ops.colwise_eval_supported(self.gar, self.h + k):
+      return self._generic_objective(honests, h_avg, direction)
+    return lambda t: ops.colwise_eval(self.gar, honests, k, self.f_decl, h_avg, direction, t)
+
+  def _median_objective(self, honests, h_avg, direction, on_device=False):
+    """The lower median of the h honest values and k copies of ONE value b is monotone in b, equals b while b lies
+    between two order statistics of the honest values and stays at them outside: median(honests + [b] * k) = middle
+    of (b, lo, hi) per coordinate, with lo / hi the medians of the honest values and k copies of -inf / +inf.  Two
+    passes over the honest rows for the whole search, then every candidate is the median of THREE rows (4 row passes
+    instead of n + 1): the same value of the rule at every coordinate — it returns one of its inputs, no arithmetic —
+    hence the same objective, bit for bit, as evaluating the rule on the n rows."""
+    ops, agg, h, k = self.ops, self.agg, self.h, self.f_real
+    n, caps = h + k, self.plan.capabilities
+    if "order_pair" in caps and ops.order_pair_supported(h):
+      lo, hi = ops.order_pair(honests, (n - 1) // 2 - k, (n - 1) // 2)   # both in one pass over the honest rows
+    else:
+      lo = agg.median(list(honests) + [torch.full_like(h_avg, -math.inf)] * k)
+      hi = agg.median(list(honests) + [torch.full_like(h_avg, math.inf)] * k)
+    if "colwise_eval" in caps:
+      # evaluate-only instances (bm_colwise_eval), nothing written: the middle of (lo, hi, candidate), else the median
+      # of the n rows themselves where the library has that instance
+      whole = not self.gar_args and ops.colwise_eval_supported("median", n)
+      if ops.colwise_eval_supported("median", 3):
+        return lambda t: ops.colwise_eval("median", [lo, hi], 1, 0, h_avg, direction, t)
+      if whole:
+        return lambda t: ops.colwise_eval("median", honests, k, self.f_decl, h_avg, direction, t)
+    return self._written_objective(lambda cand, t: agg.median([cand, lo, hi]), h_avg, direction)
+
+  def _bulyan_objective(self, honests, h_avg, direction, on_device):
+    """Bulyan's second pass needs the vectors, its ranking does not: every candidate is ranked from the scalars of ONE
+    distance pass and costs pass 2 alone (m + 1 row passes instead of n + m + 1) — ranked where the matrix is, from
+    the factor the device cursor left there (bm_attack_ranking_device: no copy, no synchronisation), or on the host
+    from the number the host's cursor proposed (one copy of the matrix per search)."""
+    ops, h, k, f = self.ops, self.h, self.f_real, self.f_decl
+    n = h + k
+    m = self.gar_args.get("m") or n - f - 2
+    sq_dev = self._unit_sqdist(honests, h_avg, direction)
+    ext = None if on_device else self._fetch(sq_dev)
+
+    def ranking(t):
+      if on_device:
+        return ops.attack_ranking_device(sq_dev, h, k, f, "bulyan", t, m)
+      order = linesearch.attack_ranking(ext, h, k, f, "bulyan", t, m)
+      return ops.index_tensor(order + [0] * (64 - n), h_avg)
+
+    if "bulyan_pass2_eval" in self.plan.capabilities and ops.bulyan_pass2_eval_supported(n, f, m, h_avg.shape[0]):
+      # pass 2 has an evaluate-only form for the shapes of the reference's experiments: the candidate in registers,
+      # the objective accumulated in the same kernel, nothing written (bm_bulyan_pass2_eval)
+      return lambda t: ops.bulyan_pass2_eval(honests, k, ranking(t), f, m, h_avg, direction, t)
+    return self._written_objective(lambda cand, t: ops.bulyan_pass2(list(honests) + [cand] * k, ranking(t), f, m),
+                                   h_avg, direction)
 
   def nesterov_lookahead(self, params, lr, worker=None):
     """params <- params - mu*lr*momentum in place (attack.py:760-767): the parameter shift before
@@ -321,65 +394,57 @@ class AggregationStep:
       sq = ops.row_sqnorms(sampled)
       agg.all_reduce_sum(sq)
       factors = ops.clip_factors_from_sq(sq, ks, self.clip)
-    # 1.+2. momentum, attack vector, sampled/honest statistics
+    # 1.+2. momentum, attack vector, sampled/honest statistics, in the form the plan chose for the first pass
     fused_defense, fused_sq = None, None
+    first_pass = self.plan.first_pass
+    searched = first_pass == "direction"
+    scale = 1.0 if searched else self.factor
     if self.momentum_at == "worker":
       if self.buffers is None:
         self.buffers = self._new_rows(h, sampled[0], zero=True)
-      fused_rule = (self.attack_evals is None and self.f_real >= 1 and not self.gar_args
-                    and self.gar in ("median", "trmean", "phocas", "meamed") and hasattr(ops, "momentum_stats_colwise"))
-      if fused_rule:  # first pass + coordinate-wise rule in one call (one kernel for median / trmean at h = 20)
+      if first_pass == "rule":  # first pass + coordinate-wise rule in one call (one kernel for median / trmean at h = 20)
         s_avg, h_avg, byz, fused_defense, out6 = ops.momentum_stats_colwise(
           sampled, self.buffers, self.mu, omd, factors, self.factor, self.attack, self.gar, self.f_decl, self.f_real)
-      elif (self.attack_evals is None and self.f_real >= 1 and self.gar in ("krum", "bulyan")
-            and not (set(self.gar_args) - {"m"}) and hasattr(ops, "momentum_stats_sqdist")):
+      elif first_pass == "sqdist":
         # first pass + the distance pass of the rule in one call (one kernel at h = 20 for long gradients)
         s_avg, h_avg, byz, fused_sq, out6 = ops.momentum_stats_sqdist(
           sampled, self.buffers, self.mu, omd, factors, self.factor, self.attack, self.f_real,
           d_total=agg._total_of(sampled))
-      elif self.attack_evals is None:
-        s_avg, h_avg, byz, out6 = ops.momentum_stats(sampled, self.buffers, self.mu, omd, factors, self.factor, self.attack)
-      else:  # the attack direction alone; the Byzantine vector follows the factor search
-        s_avg, h_avg, byz, out6 = ops.momentum_stats(sampled, self.buffers, self.mu, omd, factors, 1.0, self.attack,
-                                                     direction=True)
+      else:  # ("direction": the attack direction alone; the Byzantine vector follows the factor search)
+        s_avg, h_avg, byz, out6 = ops.momentum_stats(sampled, self.buffers, self.mu, omd, factors, scale, self.attack,
+                                                     direction=searched)
       honests = self.buffers
       s_out3, h_out3 = out6[:3], out6[3:]
     else:
       if factors is not None:
         ops.multi_scale(sampled, factors)  # in place, like the reference's grad.mul_
-      if self.momentum_at == "server" and self.server_momentum is not None:
+      if self.momentum_at == "server":
+        # (first step: grad_momentum_server is zero, attack.py:678: hon_i = (1-damp)*g_i)
+        mom = self.server_momentum if self.server_momentum is not None else torch.zeros_like(sampled[0])
         honests = self._new_rows(h, sampled[0])
-        ops.multi_fma3(honests, sampled[:h], [self.server_momentum] * h, omd, self.mu)
-      elif self.momentum_at == "server":
-        # first step: grad_momentum_server is zero (attack.py:678), hon_i = (1-damp)*g_i
-        honests = self._new_rows(h, sampled[0])
-        zero = torch.zeros_like(sampled[0])
-        ops.multi_fma3(honests, sampled[:h], [zero] * h, omd, self.mu)
+        ops.multi_fma3(honests, sampled[:h], [mom] * h, omd, self.mu)
       else:
         honests = sampled[:h]
       # momentum at the update with every sampled gradient honest: the rule, or its distance pass, is fed from the pass
       # that forms the statistics and the Byzantine vector (one pass over the rows at h = 20 / 14)
-      plain_update = (self.momentum_at == "update" and ks == h and self.attack_evals is None and self.f_real >= 1)
-      if plain_update and not self.gar_args and self.gar in ("median", "trmean", "phocas", "meamed") \
-         and hasattr(ops, "stack_stats_colwise"):
+      if ks != h and first_pass in ("rule", "sqdist"):
+        first_pass = "plain"
+      if first_pass == "rule":
         h_avg, byz, fused_defense, o6 = ops.stack_stats_colwise(honests, self.factor, self.attack, self.gar, self.f_decl,
                                                                 self.f_real)
         h_out3 = o6[3:]
-      elif plain_update and self.gar in ("krum", "bulyan") and not (set(self.gar_args) - {"m"}) \
-          and hasattr(ops, "stack_stats_sqdist"):
+      elif first_pass == "sqdist":
         h_avg, byz, fused_sq, o6 = ops.stack_stats_sqdist(honests, self.factor, self.attack, self.f_real,
                                                           d_total=agg._total_of(sampled))
         h_out3 = o6[3:]
-      elif self.attack_evals is None:
-        h_avg, h_out3, byz = ops.stack_stats(honests, scale=self.factor, attack=self.attack)
       else:
-        h_avg, h_out3, byz = ops.stack_stats(honests, scale=1.0, attack=self.attack, direction=True)
+        h_avg, h_out3, byz = ops.stack_stats(honests, scale=scale, attack=self.attack, direction=searched)
       if self.momentum_at == "update" and ks == h:
         # the honest stack IS the sampled stack (attack.py:809-810): one pass gives both sets of statistics
         s_avg, s_out3 = h_avg, h_out3
       else:
         s_avg, s_out3 = ops.stack_stats(sampled)
-    if self.attack_evals is not None and self.f_real > 0:
+    if searched and self.f_real > 0:
       direction = byz
       factor = self._search_factor(honests, h_avg, direction)  # a number, or the device search's tensor ([0]: the factor)
       self.last_factor = factor
@@ -447,7 +512,7 @@ class AggregationStep:
     self._update = defense
     self.last_byzantine = byz
     self._pending = dict(packed=stats, prev=self._prev_stats if count > 0 else None, npast=2 if count > 0 else 0,
-                         has_attack=self.f_real > 0, has_l2=params is not None and origin is not None, ks=ks,
+                         has_l2=params is not None and origin is not None, ks=ks,
                          floats=None)
     if self.nb_past > 0:
       self.pasts.appendleft(s_avg)
@@ -462,59 +527,69 @@ class AggregationStep:
   # ------------------------------------------------------------------------ #
 
   def _exchange(self, pend):
-    """One packed exchange of every scalar of the step: sums and maxima, all ranks."""
-    st = pend["study"]  # layout: include/bm_gar.h (bm_study_stats)
-    sums = [pend["s"][:2], pend["h"][:2], st[:20], st[22:23]]
-    maxes = [pend["s"][2:], pend["h"][2:], st[20:22]]
-    if pend["prev_s2"] is not None:
-      sums.append(pend["prev_s2"])
-    # ONE copy to the host, ONE synchronisation: sums and maxima leave the device together (two `tolist()` were two
-    # copies with a host round trip between them: ~30 us of a 0.95 ms step, profiles/r05_c_full_kernel_trace.csv), and
-    # the whole tensors travel — three or four of them in one concatenation — to be taken apart on the host (eight
-    # slices were two batched-copy launches)
+    """One packed exchange of every scalar of the sequence (sums and maxima, all ranks), as a _StudyRecord."""
+    s3, h3, st, prev = pend["s"], pend["h"], pend["study"], pend["prev_s2"]
+    last = [prev] if prev is not None else []
     if not self.agg.collective:
-      parts = [pend["s"], pend["h"], st] + ([pend["prev_s2"]] if pend["prev_s2"] is not None else [])
-      flat = torch.cat(parts).tolist()
-      s3, h3, stl = flat[0:3], flat[3:6], flat[6:6 + int(st.numel())]
-      host_sums = s3[:2] + h3[:2] + stl[:20] + stl[22:23] + (flat[6 + int(st.numel()):] if pend["prev_s2"] is not None else [])
-      return host_sums, s3[2:] + h3[2:] + stl[20:22]
-    sums, maxes = self.agg.exchange(torch.cat(sums), torch.cat(maxes))
-    ns = int(sums.numel())
-    flat = torch.cat([sums, maxes]).tolist()
-    return flat[:ns], flat[ns:]
+      # ONE copy to the host, ONE synchronisation: the whole tensors travel — three or four of them in one concatenation
+      # — to be taken apart on the host (two `tolist()` were two copies with a host round trip between them: ~30 us of a
+      # 0.95 ms step, profiles/r05_c_full_kernel_trace.csv; eight slices were two batched-copy launches)
+      flat = torch.cat([s3, h3, st] + last).tolist()
+      s3, h3, st, last = flat[0:3], flat[3:6], flat[6:6 + _lib.STUDY_SLOTS], flat[6 + _lib.STUDY_SLOTS:]
+      sums = s3[_lib.OUT3_SUMS] + h3[_lib.OUT3_SUMS] + st[_lib.STUDY_SUMS] + st[_lib.STUDY_L2] + last
+      maxes = s3[_lib.OUT3_MAX] + h3[_lib.OUT3_MAX] + st[_lib.STUDY_MAXES]
+    else:
+      sums, maxes = self.agg.exchange(
+        torch.cat([s3[_lib.OUT3_SUMS], h3[_lib.OUT3_SUMS], st[_lib.STUDY_SUMS], st[_lib.STUDY_L2]] + last),
+        torch.cat([s3[_lib.OUT3_MAX], h3[_lib.OUT3_MAX], st[_lib.STUDY_MAXES]]))
+      ns = int(sums.numel())
+      flat = torch.cat([sums, maxes]).tolist()
+      sums, maxes = flat[:ns], flat[ns:]
+    s2, sd, h2, hd = sums[0:4]
+    st = sums[4:24]  # STUDY_SUMS: the slots of bm_study_stats keep their places
+    gram, (ex0, ex1), (a2, ad) = st[_lib.STUDY_GRAM], st[_lib.STUDY_EX], st[_lib.STUDY_ATTACK]
+    smax, hmax, amax, dmax = maxes
+    return _StudyRecord(s2, sd, smax, h2, hd, hmax, a2, ad, amax, gram[4 * 2 + 2], dmax, sums[24], gram, ex0, ex1,
+                        sums[25] if prev is not None else math.nan)
 
-  def _floats_from_packed(self, pend):
-    """Decode the statistics vector of bm_step_worker (layout: include/bm_gar.h)."""
+  @staticmethod
+  def _unpack(pend):
+    """The statistics vector of bm_step_worker as a _StudyRecord."""
     vec = pend["packed"] if pend["prev"] is None else torch.cat([pend["packed"], pend["prev"][:1]])
     v = vec.tolist()  # the only synchronisation
+    L = _lib
+    return _StudyRecord(v[L.STEP_S2], v[L.STEP_SD], v[L.STEP_SMAX], v[L.STEP_H2], v[L.STEP_HD], v[L.STEP_HMAX],
+                        v[L.STEP_A2], v[L.STEP_AD], v[L.STEP_AMAX], v[L.STEP_D2], v[L.STEP_DMAX], v[L.STEP_L2],
+                        v[L.STEP_GRAM], v[L.STEP_EX.start], v[L.STEP_EX.start + 1],
+                        v[len(pend["packed"])] if pend["prev"] is not None else math.nan)
+
+  def _study_floats(self, rec, pend):
+    """The study row (attack.py:828-868) from the scalars of either path."""
     nan = math.nan
-    att, k_s, k_h, k_a = pend["has_attack"], pend["ks"], self.h, self.f_real
+    att, k_s, k_h, k_a = self.f_real > 0, pend["ks"], self.h, self.f_real
+    g = rec.gram
 
     def dev(x, k):
       return math.sqrt(x / (k - 1)) if k >= 2 else nan
 
     def cos(i, j):
-      if not att and 3 in (i, j):
+      if not att and 3 in (i, j):  # (no attack: no fourth vector)
         return nan
-      return v[8 + 4 * i + j] / math.sqrt(v[8 + 5 * i]) / math.sqrt(v[8 + 5 * j])
+      return g[4 * i + j] / math.sqrt(g[5 * i]) / math.sqrt(g[5 * j])
 
-    res = {
-      "l2_origin": math.sqrt(v[7]) if pend["has_l2"] else nan,
-      "sampled_norm_avg": math.sqrt(v[0]), "sampled_norm_dev": dev(v[1], k_s), "sampled_norm_max": v[26],
-      "honest_norm_avg": math.sqrt(v[2]), "honest_norm_dev": dev(v[3], k_h), "honest_norm_max": v[27],
-      "attack_norm_avg": math.sqrt(v[5]) if att else nan, "attack_norm_dev": dev(v[6], k_a) if att else nan,
-      "attack_norm_max": v[29] if att else nan,
-      "defense_norm_avg": math.sqrt(v[4]), "defense_norm_max": v[28],
+    past = pend["npast"] > 0
+    return {
+      "l2_origin": math.sqrt(rec.l2) if pend["has_l2"] else nan,
+      "sampled_norm_avg": math.sqrt(rec.s2), "sampled_norm_dev": dev(rec.sd, k_s), "sampled_norm_max": rec.smax,
+      "honest_norm_avg": math.sqrt(rec.h2), "honest_norm_dev": dev(rec.hd, k_h), "honest_norm_max": rec.hmax,
+      "attack_norm_avg": math.sqrt(rec.a2) if att else nan, "attack_norm_dev": dev(rec.ad, k_a) if att else nan,
+      "attack_norm_max": rec.amax if att else nan,
+      "defense_norm_avg": math.sqrt(rec.d2), "defense_norm_max": rec.dmax,
       "cosin_splhon": cos(0, 1), "cosin_spldef": cos(0, 2), "cosin_hondef": cos(1, 2),
       "cosin_splatt": cos(0, 3), "cosin_honatt": cos(1, 3), "cosin_attdef": cos(3, 2),
+      "cosin_sampled": rec.ex0 / math.sqrt(rec.s2) / math.sqrt(rec.prev_s2) if past else nan,
+      "curv_sampled": self.mu * rec.ex1 if past else nan,
     }
-    if pend["npast"] > 0:
-      res["cosin_sampled"] = v[24] / math.sqrt(v[0]) / math.sqrt(v[32])
-      res["curv_sampled"] = self.mu * v[25]
-    else:
-      res["cosin_sampled"] = nan
-      res["curv_sampled"] = nan
-    return res
 
   def floats(self):
     """Python floats of the study row (attack.py:828-868) for the last run(); synchronises once.
@@ -522,52 +597,8 @@ class AggregationStep:
     pend = self._pending
     if pend is None:
       raise RuntimeError("floats() needs a run() first")
-    if pend["floats"] is not None:
-      return pend["floats"]
-    if self.gar == "brute":
-      self.agg.check_brute()  # (a step replayed from a HIP graph could not check inside run(): here at the latest)
-    if "packed" in pend:
-      pend["floats"] = self._floats_from_packed(pend)
-      return pend["floats"]
-    sums, maxes = self._exchange(pend)
-    s2, sd, h2, hd = sums[0:4]
-    st = sums[4:24]          # Gram 4 x 4 | <s, past>, <s, C> | sum avg_a^2, sum_i |a_i - avg_a|^2
-    att = self.f_real > 0
-    nc = 4 if att else 3
-    g = [[st[4 * a + b] for b in range(4)] for a in range(4)]
-    ex = st[16:18]
-    d2 = g[2][2]
-    a2, ad = (st[18], st[19]) if att else (math.nan, math.nan)
-    l2 = math.sqrt(sums[24]) if pend["has_l2"] else math.nan
-    prev_norm = math.sqrt(sums[25]) if pend["prev_s2"] is not None else math.nan
-    smax, hmax = maxes[0], maxes[1]
-    amax = maxes[2] if att else math.nan
-    dmax = maxes[3]
-    k_s, k_h, k_a = pend["ks"], self.h, self.f_real
-
-    def dev(v, k):
-      return math.sqrt(v / (k - 1)) if k >= 2 else math.nan
-
-    def cos(i, j):
-      if i >= nc or j >= nc:
-        return math.nan
-      return g[i][j] / math.sqrt(g[i][i]) / math.sqrt(g[j][j])
-
-    res = {
-      "l2_origin": l2,
-      "sampled_norm_avg": math.sqrt(s2), "sampled_norm_dev": dev(sd, k_s), "sampled_norm_max": smax,
-      "honest_norm_avg": math.sqrt(h2), "honest_norm_dev": dev(hd, k_h), "honest_norm_max": hmax,
-      "attack_norm_avg": math.sqrt(a2) if att else math.nan,
-      "attack_norm_dev": dev(ad, k_a) if att else math.nan, "attack_norm_max": amax,
-      "defense_norm_avg": math.sqrt(d2), "defense_norm_max": dmax,
-      "cosin_splhon": cos(0, 1), "cosin_spldef": cos(0, 2), "cosin_hondef": cos(1, 2),
-      "cosin_splatt": cos(0, 3), "cosin_honatt": cos(1, 3), "cosin_attdef": cos(3, 2),
-    }
-    if pend["npast"] > 0:
-      res["cosin_sampled"] = ex[0] / math.sqrt(s2) / prev_norm
-      res["curv_sampled"] = self.mu * ex[1]
-    else:
-      res["cosin_sampled"] = math.nan
-      res["curv_sampled"] = math.nan
-    pend["floats"] = res
-    return res
+    if pend["floats"] is None:
+      if self.gar == "brute":
+        self.agg.check_brute()  # (a step replayed from a HIP graph could not check inside run(): here at the latest)
+      pend["floats"] = self._study_floats(self._unpack(pend) if "packed" in pend else self._exchange(pend), pend)
+    return pend["floats"]
