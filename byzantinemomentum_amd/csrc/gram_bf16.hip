@@ -396,7 +396,8 @@ __global__ __launch_bounds__(64 * kB3Waves, (B3Shape<K, NPL>::MINW)) void gram3_
 // sq[i][j] = G_ii + G_jj - 2 G_ij in fp64, by one workgroup of kSqThreads lanes.  Also decides whether the Gram form
 // was accurate enough: its absolute error is ~eps_G * (G_ii + G_jj) (eps_G ~ 6e-9, measured), so a pair
 // whose squared distance is below tau * (G_ii + G_jj) — two rows that nearly coincide relative to
-// their (centred) norms — has lost relative accuracy eps_G / tau.  The rows of such pairs are listed in
+// their (centred) norms — has lost relative accuracy eps_G / tau (eps_G is that of long rows; short ones are held to a
+// wider tau by the caller: gate_tau, pairwise.hip).  The rows of such pairs are listed in
 // `sub` (sub[0] = count, sub[1..] = indices, ascending); the caller recomputes the distances among them
 // with the direct-difference kernel (pairwise.hip), which has no cancellation: near-duplicate rows
 // lie close to EACH OTHER, so that sub-stack is exactly where the Gram form cannot be trusted.

@@ -504,6 +504,21 @@ static int pairwise_direct(const float* const* rows, int n, int64_t d, double* s
 }  // namespace bm
 
 namespace bm {
+// The accuracy gate's threshold for rows of d coordinates.  BM_PAIR_TAU (2e-3) is sized for the Gram form's error on
+// LONG rows, ~6e-9 (G_ii + G_jj): many per-wave fp32 sums meet in fp64 and their roundings average out.  A short row is
+// a few fp32 chunk results — one at d <= 64, each good to ~2^-23 = 1.2e-7 of its Gram entries (the roundings of the
+// MFMA chains and of the fold) — so the error falls like 1.2e-7 / sqrt(d / 64) only, and a pair just above 2e-3 was
+// off by up to 6e-5 of its squared distance at d = 1 (tests/test_gpu_distance_matrix.py measured 2.1e-5).  The gate
+// therefore opens to 0.1 / sqrt(chunks): 2 * 1.2e-7 / 0.1 = 2.4e-6 of a distance at worst, whatever d; from 2 500
+// chunks (d = 160 000) on it is BM_PAIR_TAU itself.  The rows it lists on top cost nothing at these lengths.
+static double gate_tau(int64_t d) {
+  const double base = tuning().pair_tau;
+  if (base <= 0.0) return base;  // (the gate is off)
+  const int64_t chunks = d > 64 ? (d + 63) / 64 : 1;
+  const double short_rows = 0.1 / sqrt((double)chunks);
+  return base > short_rows ? base : short_rows;
+}
+
 // The default distance pass (BM_PAIR_MODE 0): the Gram kernel, the reduction of its partial matrices with the
 // squared distances and the accuracy gate's row list (last-arriving workgroup), the gated direct kernel — which
 // returns at once unless rows were listed — and, with `rank`, the ranking of the rows inside that third launch.
@@ -512,7 +527,7 @@ static int pairwise_gram_path(const float* const* rows, int n, int64_t d, int64_
   int* flag = static_cast<int*>(ws);  // flag[0] = rows to recompute, flag[1..] = their indices; counters behind them
   double* gram_partial = reinterpret_cast<double*>(static_cast<char*>(ws) + 512);
   double* direct_partial = gram_partial + pair_gram_doubles(n);
-  const double tau = tuning().pair_tau;
+  const double tau = gate_tau(d);
   int blocks = 0;
   int rc = gram3_partials(rows, n, d, d_total, gram_partial, flag, &blocks, s);
   if (rc != 0) return rc;
@@ -558,7 +573,7 @@ int pairwise_from_gram_partials(const float* const* rows, int n_full, int nc, in
   double* gram_partial = pairwise_gram_area(ws);
   double* direct_partial = gram_partial + pair_gram_doubles(n_full);
   double* gram = gram_partial + gram3_partial_doubles(n_full);
-  const double tau = tuning().pair_tau;
+  const double tau = gate_tau(d);
   int rc = gram_finish(gram_partial, blocks, nc, n_full, gram, sq_nxn, flag, tau, s);
   if (rc != 0 || tau <= 0.0) return rc;
   return pairwise_direct(rows, n_full, d, sq_nxn, direct_partial, flag, s);

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from oracle import gar_oracle as O
+from tests.distance_matrix import sqdist_f64_on_gpu  # (test_gpu_parity_r3.py imports it from here too)
 from tests.golden_io import CASES, Golden, same_bits
 from tests.instance_matrix import sorted_window, window_candidates as _window_candidates
 
@@ -54,20 +55,6 @@ def gpu_stack(kind, n, f, d, seed):
     acc += g
   byz = acc.div_(h).mul_(-0.1)
   return honest + [byz] * f, h
-
-
-def sqdist_f64_on_gpu(rows):
-  """n x n float64 squared distances, direct differences in fp64 on the GPU (no Gram, no cancellation)."""
-  n = len(rows)
-  st = torch.stack([r.double() for r in rows])
-  out = np.zeros((n, n))
-  for i in range(n - 1):
-    diff = st[i + 1:] - st[i]
-    vals = (diff * diff).sum(dim=1).cpu().numpy()
-    out[i, i + 1:] = vals
-    out[i + 1:, i] = vals
-    del diff
-  return out
 
 
 def decisive(scores, k, tol=1e-5):
