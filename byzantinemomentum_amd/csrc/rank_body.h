@@ -115,6 +115,22 @@ __device__ __forceinline__ void krum_rank_body(const double* __restrict__ sq, in
   krum_rank_from_distances(lds, n, f, m, mode, order, scores_out, bitonic);
 }
 
+// Stable argsort of n (<= BM_MAX_ROWS) fp64 keys, lane i of the workgroup's first wave holding key i: order[rank] = i
+// with ties to the lower index and NaN keys last (as +inf).  k: BM_MAX_ROWS doubles of LDS, left holding the keys as
+// they were compared.  Every lane of the workgroup must call (a barrier inside); `order` may be LDS or device memory.
+// The body of stable_argsort_kernel (reduce.hip) and of the ranking of the anticge attack (anticge.hip).
+__device__ __forceinline__ void stable_argsort_body(double key, int n, double* k, int32_t* order) {
+  const int i = threadIdx.x;
+  if (i < n) k[i] = (key != key) ? __builtin_inf() : key;
+  __syncthreads();
+  if (i < n) {
+    const double ki = k[i];
+    int rank = 0;
+    for (int j = 0; j < n; ++j) rank += (k[j] < ki || (k[j] == ki && j < i)) ? 1 : 0;
+    order[rank] = i;
+  }
+}
+
 // BM_RANK_ALGO: 0 (default) = by row count, 1 = bitonic, 2 = counting (A/B)
 inline bool rank_bitonic(int n) {
   const int algo = tuning().rank_algo;

@@ -9,6 +9,7 @@
 // Each is ONE pass over its inputs with every reduction deterministic (fixed trees, fp64
 // across lanes/workgroups, no float atomics) and no host synchronisation.
 #include "bm_common.h"
+#include "rank_body.h"
 
 namespace bm {
 
@@ -467,19 +468,7 @@ __global__ __launch_bounds__(kRedBlock) void multi_axpby_kernel(AxpbyTable tab, 
 __global__ __launch_bounds__(64) void stable_argsort_kernel(const double* __restrict__ keys, int n,
                                                             int32_t* __restrict__ order) {
   __shared__ double k[BM_MAX_ROWS];
-  const int i = threadIdx.x;
-  if (i < n) {
-    double v = keys[i];
-    if (v != v) v = __builtin_inf();
-    k[i] = v;
-  }
-  __syncthreads();
-  if (i < n) {
-    const double ki = k[i];
-    int rank = 0;
-    for (int j = 0; j < n; ++j) rank += (k[j] < ki || (k[j] == ki && j < i)) ? 1 : 0;
-    order[rank] = i;
-  }
+  stable_argsort_body((int)threadIdx.x < n ? keys[threadIdx.x] : 0.0, n, k, order);
 }
 
 int64_t stats_workspace_bytes() { return (int64_t)kStatsCaps.sets() * 3 * (int64_t)sizeof(double); }

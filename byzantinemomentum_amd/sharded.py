@@ -112,7 +112,7 @@ class HipBackend:
   # the optional legs step.AggregationStep plans with (read once, in its constructor); each names a method below
   capabilities = frozenset((
     "step_worker", "momentum_stats_colwise", "momentum_stats_sqdist", "stack_stats_colwise", "stack_stats_sqdist",
-    "device_search", "attack_ranking_device", "bulyan_pass2_eval", "order_pair", "colwise_eval", "sqdist2"))
+    "device_search", "attack_ranking_device", "bulyan_pass2_eval", "order_pair", "colwise_eval", "sqdist2", "anticge"))
 
   def __init__(self):
     from . import gars, stats
@@ -220,6 +220,13 @@ class HipBackend:
   def study_stats(self, *args, **kwargs):
     return self.stats.study_stats(*args, **kwargs)
 
+  def anticge(self, honests, f_decl, reduce):
+    """The vector of the `anticge` attack on this device's slice of the honest gradients (stats.anticge_sum /
+    anticge_scale); reduce(t): the in-place sum over the ranks of a small device tensor, the identity with one rank."""
+    byz, _, scal = self.stats.anticge_sum(honests, f_decl, reduce(self.row_sqnorms(honests)))
+    reduce(scal[:1])
+    return self.stats.anticge_scale(byz, scal)
+
   def colwise_eval_supported(self, rule, n):
     return self.stats.colwise_eval_supported(rule, n)
 
@@ -250,6 +257,27 @@ class HipBackend:
   def step_worker(self, comm, *args, **kwargs):
     """One whole step with worker-side momentum in one C call (bm_step_worker)."""
     return self.stats.step_worker(comm, *args, **kwargs)
+
+
+def _anticge_sum_torch(backend, local, f_decl, sq):
+  """bm_anticge_sum in plain torch for a backend without the kernel: (S, order, [sum S^2 here, |g_(maxpos)|^2])."""
+  h = len(local)
+  maxpos = h - f_decl
+  keys = torch.where(torch.isfinite(sq[:h]), sq[:h], torch.full_like(sq[:h], math.inf))
+  order = backend.argsort(keys, h)
+  ranked = order[:h].tolist()
+  attack = local[ranked[0]].clone()
+  for i in ranked[:maxpos]:  # (the smallest row a second time first: anticge.py:70-72)
+    attack.add_(local[i])
+  return attack, order, torch.stack([attack.double().pow(2).sum(), keys[ranked[maxpos]]])
+
+
+def _anticge_scale_torch(vec, scal):
+  """bm_anticge_scale in plain torch: the norms as fp32 numbers, nextafter and quotient in double (anticge.py:68,74-76)."""
+  attnorm, byznorm = scal.sqrt().float().tolist()
+  if attnorm > 0:
+    vec.mul_(-math.nextafter(byznorm, 0) / attnorm)
+  return vec
 
 
 class ShardedAggregator:
@@ -529,6 +557,26 @@ class ShardedAggregator:
     sq = self.backend.row_sqnorms(local)
     self._all_reduce(sq)
     return self.backend.selected_mean(local, self.backend.argsort(sq, n), n - f)
+
+  def anticge(self, local_honests, f_decl, f_real):
+    """The reference's `anticge` attack (attacks/anticge.py:49-78) on this rank's slice of the honest gradients:
+    `f_real` references to ONE new vector.  Row norms -> all-reduce -> rank and sum the selected rows -> all-reduce of
+    the ONE scalar |S|^2 -> scale: two small collectives, never a d-sized one, none with one rank.  A backend that
+    declares the "anticge" capability runs the two legs as kernels (HipBackend.anticge); any other gets
+    the same steps in plain torch over its `row_sqnorms` and `argsort` legs."""
+    local = list(local_honests)
+    h = len(local)
+    if f_real <= 0:
+      return []
+    if f_real > f_decl:  # anticge.py:60-63: a Byzantine gradient is selected whatever it is
+      return [torch.full_like(local[0], math.nan)] * f_real
+    if not 1 <= f_decl <= h:
+      raise ValueError(f"anticge needs 1 <= f_decl <= {h} honest gradients, got f_decl = {f_decl}")
+    if "anticge" in getattr(self.backend, "capabilities", ()):
+      return [self.backend.anticge(local, f_decl, self._all_reduce)] * f_real
+    byz, _, scal = _anticge_sum_torch(self.backend, local, f_decl, self._all_reduce(self.backend.row_sqnorms(local)))
+    self._all_reduce(scal[:1])
+    return [_anticge_scale_torch(byz, scal)] * f_real
 
   def compute_avg_dev_max(self, local_samples):
     """Sharded tools.compute_avg_dev_max: (local slice of the average, norm, deviation, max)."""

@@ -17,7 +17,7 @@ from . import gars
 
 __all__ = ["compute_avg_dev_max", "stack_stats_async", "study_dots", "study_stats", "multi_axpby", "row_sqnorms", "momentum_stats", "momentum_stats_colwise", "momentum_stats_sqdist", "stack_stats_colwise", "stack_stats_sqdist",
            "multi_fma3", "clip_factors", "clip_factors_from_sq", "multi_scale", "clip_gradients", "l2_distance",
-           "step_worker"]
+           "step_worker", "anticge_sum", "anticge_scale", "anticge_attack"]
 
 _ptr = gars._ptr
 
@@ -275,6 +275,59 @@ def row_sqnorms(gradients):
     _lib.check(lib.bm_row_sqnorms(_lib.pointer_table(gradients), n, d, _ptr(res), _ptr(ws), gars._stream(device)),
                "bm_row_sqnorms")
   return res[:n]
+
+
+def anticge_sum(gradients, f_decl, row_sq):
+  """First leg of the `anticge` attack (attacks/anticge.py:64-72, bm_anticge_sum) from the honest gradients and their
+  squared norms `row_sq` (device fp64, what row_sqnorms returns; the global ones under sharding): the rows are ranked by
+  norm on the device and the selected ones summed in the reference's order.  Returns (S, order, scal): the unscaled
+  attack vector (a fresh tensor), the ranking (int32[MAX_ROWS]) and the device fp64 pair [sum S^2 over these
+  coordinates, squared norm of the first row left out] that anticge_scale reads.  No sync."""
+  h, d, device = gars._validate(gradients)
+  if not 1 <= f_decl <= h:
+    raise gars.GarInputError(f"anticge needs 1 <= f_decl <= {h} honest gradients, got f_decl = {f_decl}")
+  if not (isinstance(row_sq, torch.Tensor) and row_sq.device == device and row_sq.dtype == torch.float64
+          and row_sq.numel() >= h and row_sq.is_contiguous()):
+    raise gars.GarInputError("anticge_sum: row_sq must be a contiguous float64 tensor of h squared norms on the gradients' device")
+  lib = _lib.load()
+  out = torch.empty(d, dtype=torch.float32, device=device)
+  order = torch.empty(_lib.MAX_ROWS, dtype=torch.int32, device=device)
+  scal = torch.empty(2, dtype=torch.float64, device=device)
+  ws = gars._Scratch.get(device, "ws_anticge", nbytes=int(lib.bm_anticge_workspace_bytes(d)))
+  with torch.cuda.device(device):
+    _lib.check(lib.bm_anticge_sum(_lib.pointer_table(gradients), h, d, int(f_decl), _ptr(row_sq), _ptr(out), _ptr(order),
+                                  _ptr(scal), _ptr(ws), gars._stream(device)), "bm_anticge_sum")
+  return out, order, scal
+
+
+def anticge_scale(vec, scal):
+  """Second leg (attacks/anticge.py:68,74-76, bm_anticge_scale): vec *= -nextafter(norm_(maxpos), 0) / |S| in place, the
+  multiplier formed on the device from `scal` of anticge_sum (scal[0] all-reduced first under sharding).  No sync."""
+  _, d, device = gars._validate([vec])
+  _require_scalar_on(scal, device, "anticge_scale: scal must be a contiguous float64 tensor on the vector's device")
+  if scal.numel() < 2:
+    raise gars.GarInputError("anticge_scale: scal must hold the two scalars anticge_sum left")
+  lib = _lib.load()
+  gars.invalidate_rank_cache()
+  with torch.cuda.device(device):
+    _lib.check(lib.bm_anticge_scale(_ptr(vec), d, _ptr(scal), gars._stream(device)), "bm_anticge_scale")
+  return vec
+
+
+def anticge_attack(grad_honests, f_decl, f_real, **kwargs):
+  """Drop-in for the reference's `anticge` attack (attacks/anticge.py:49-78): `f_real` references to ONE new tensor,
+  the negated sum of the h - f_decl honest gradients of smallest norm (the smallest counted twice, as the reference
+  does), scaled to just below the norm of the next one.  f_real > f_decl: the all-NaN vector of anticge.py:60-63.
+  Row norms, ranking, sum, norm and scaling all run on the device, on the current stream, without a synchronisation.
+  **kwargs: ignored, like the keyword arguments the reference's attacks are handed and do not know (attacks/__init__.py:15-17)."""
+  grad_honests = list(grad_honests)
+  h, d, device = gars._validate(grad_honests)
+  if f_real <= 0:
+    return []
+  if f_real > f_decl:
+    return [torch.full_like(grad_honests[0], math.nan)] * f_real
+  byz, _, scal = anticge_sum(grad_honests, f_decl, row_sqnorms(grad_honests).contiguous())
+  return [anticge_scale(byz, scal)] * f_real
 
 
 def multi_axpby(ys, xs, a, b):

@@ -8,6 +8,8 @@ Given the sampled honest gradients of a step it performs, without leaving the GP
   2. the "empire" / "little" attack  byz = avg_h + factor*dir, repeated f_real times   attacks/identical.py:63-86,129-141
                                    factor fixed, or searched within `attack_evals` evaluations of
                                    |GAR(honests + [avg_h + t*dir]*f) - avg_h|^2         attacks/identical.py:67-77
+     or the "anticge" attack       byz = -(sum of the h - f_decl smallest honests), scaled to just below the next norm,
+                                   repeated f_real times; no factor                     attacks/anticge.py:49-78
   3. the aggregation rule          defense = GAR(honests + [byz]*f, f)                 attack.py:821
   4. the momentum of the update    server: M <- defense; update: M <- mu*M + (1-damp)*defense   attack.py:832-839
   5. the study statistics          sampled / honest / attack stacks, defense norm and max, six cosines,
@@ -71,6 +73,9 @@ class AggregationStep:
     single_call: with the HIP backend, worker-side momentum and a rule the C entry point knows
     (krum, bulyan, median, trmean, phocas, meamed), run() is ONE call into libbm_gar.so (bm_step_worker),
     collectives included; False keeps the kernel-by-kernel Python sequence (same kernels, same results).
+    attack: "empire" / "little" (attacks/identical.py), or "anticge" (attacks/anticge.py: no factor — `attack_factor` is
+    ignored, `attack_evals` must be None, and 1 <= nb_decl_byz <= honest workers); it runs as its own short chain behind
+    the plain first pass (ShardedAggregator.anticge), with every momentum placement, clipping and rule.
     attack_evals: None = the fixed `attack_factor`; a positive integer E = the reference's `factor:-E` (its
     default is -16): the factor is searched each step with tools.line_maximize's exploration
     (identical.py:67-77), `attack_negative` being the attack's `negative` argument during the search.
@@ -84,10 +89,17 @@ class AggregationStep:
       raise ValueError(f"unknown aggregation rule {gar!r}")
     if momentum_at not in ("worker", "server", "update"):
       raise ValueError(f"momentum_at must be 'worker', 'server' or 'update', got {momentum_at!r}")
-    if attack not in ("empire", "little"):
-      raise ValueError(f"unknown attack {attack!r} (empire: factor, little: factor, use a negative one for negative:True)")
+    if attack not in ("empire", "little", "anticge"):
+      raise ValueError(f"unknown attack {attack!r} (empire: factor, little: factor, use a negative one for negative:True; "
+                       f"anticge: no factor)")
     if attack_evals is not None and (not isinstance(attack_evals, int) or attack_evals < 1):
       raise ValueError(f"attack_evals must be a positive number of evaluations, got {attack_evals!r}")
+    if attack == "anticge":
+      if attack_evals is not None:
+        raise ValueError("the anticge attack has no factor to search: attack_evals must be None")
+      if nb_real_byz >= 1 and not 1 <= nb_decl_byz <= nb_workers - nb_real_byz:
+        raise ValueError(f"the anticge attack needs 1 <= nb_decl_byz <= {nb_workers - nb_real_byz} honest workers "
+                         f"(attacks/anticge.py:67-68 indexes the sorted norms at h - f_decl), got {nb_decl_byz}")
     if line_search not in ("auto", "host", "generic"):
       raise ValueError(f"line_search must be 'auto', 'host' or 'generic', got {line_search!r}")
     if not 0 <= nb_past <= MAX_PAST:
@@ -142,6 +154,8 @@ class AggregationStep:
     stem = {"worker": "momentum_stats_", "update": "stack_stats_"}.get(self.momentum_at)
     if not fixed:
       first_pass = "direction"
+    elif self.attack == "anticge":  # its own chain behind the plain first pass, which forms no attack vector
+      first_pass = "plain"
     elif stem and k >= 1 and not self.gar_args and gar in _COLWISE and stem + "colwise" in caps:
       first_pass = "rule"
     elif stem and k >= 1 and only_m and gar in _DISTANCE and stem + "sqdist" in caps:
@@ -165,7 +179,7 @@ class AggregationStep:
       search = "colwise_eval"
     else:
       search = "generic"
-    single = bool(single_call and fixed and self.momentum_at == "worker" and "step_worker" in caps
+    single = bool(single_call and fixed and self.attack != "anticge" and self.momentum_at == "worker" and "step_worker" in caps
                   and gar in _DISTANCE + _COLWISE and only_m and (not self.agg.collective or self.agg.native is not None))
     return StepPlan(only_m, analytic, first_pass, search, device_cursor, single, caps)
 
@@ -398,7 +412,8 @@ class AggregationStep:
     fused_defense, fused_sq = None, None
     first_pass = self.plan.first_pass
     searched = first_pass == "direction"
-    scale = 1.0 if searched else self.factor
+    anticge = self.attack == "anticge"
+    scale = None if anticge else (1.0 if searched else self.factor)  # None: the first pass forms no attack vector
     if self.momentum_at == "worker":
       if self.buffers is None:
         self.buffers = self._new_rows(h, sampled[0], zero=True)
@@ -438,12 +453,17 @@ class AggregationStep:
                                                           d_total=agg._total_of(sampled))
         h_out3 = o6[3:]
       else:
-        h_avg, h_out3, byz = ops.stack_stats(honests, scale=scale, attack=self.attack, direction=searched)
+        h_avg, h_out3, *byz = ops.stack_stats(honests, scale=scale, attack=self.attack, direction=searched)
+        byz = byz[0] if byz else None
       if self.momentum_at == "update" and ks == h:
         # the honest stack IS the sampled stack (attack.py:809-810): one pass gives both sets of statistics
         s_avg, s_out3 = h_avg, h_out3
       else:
         s_avg, s_out3 = ops.stack_stats(sampled)
+    if anticge and self.f_real > 0:
+      # attacks/anticge.py:49-78 on the honest gradients the rule is about to see (the updated buffers under worker
+      # placement): row norms, ranking, sum and scaling on the device, two small collectives under sharding
+      byz = agg.anticge(honests, self.f_decl, self.f_real)[0]
     if searched and self.f_real > 0:
       direction = byz
       factor = self._search_factor(honests, h_avg, direction)  # a number, or the device search's tensor ([0]: the factor)

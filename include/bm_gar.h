@@ -44,7 +44,7 @@ enum bm_colwise_op {
   BM_OP_MEAMED = 3  /* aggregators/trmean.py:96-109 n-f closest to the median        */
 };
 
-/* ABI version of this header; bumped on any signature change. */
+/* ABI version of this header; bumped on any signature change (23 also covers the additions that say so below). */
 int bm_abi_version(void);
 /* TEST / MEASUREMENT ONLY — not part of the drop-in surface.  Sets one launch-shape knob by the name of its environment
  * variable (BM_COL_BURST, BM_PAIR_MODE, BM_BRUTE_BUDGET, ...: csrc/bm_common.h, struct Tuning) for the calls that
@@ -196,6 +196,29 @@ int bm_row_sqnorms(const float* const* rows, int k, int64_t d, double* sq_out, v
 /* order_out = stable argsort (ties to the lower index, NaN last) of n fp64 keys that live on
  * the device: the `d.sort(key=...)` of aggregators/aksel.py:48 without a host round trip. */
 int bm_stable_argsort(const double* keys, int n, int32_t* order_out, void* stream);
+
+/* The reference's `anticge` attack (attacks/anticge.py:49-78) on the device, for 1 <= f_decl <= h (the reference indexes
+ * normed[h - f_decl]).  These three entry points joined ABI 23: additions only, no signature changed.
+ *   With maxpos = h - f_decl and g_(0), g_(1), ... the honest rows by increasing norm (a non-finite norm counts as +inf,
+ *   ties go to the lower index: anticge.py:44-47 and Python's stable sort):
+ *     S   = ((g_(0) + g_(0)) + g_(1)) + ... + g_(maxpos-1)      sequential fp32, the smallest row twice: anticge.py:70-72
+ *           (`attack = g_(0).clone()`, then one add_ per selected row, g_(0) first; maxpos = 0 leaves the clone alone)
+ *     byz = S * (float)(-nextafter(|g_(maxpos)|, 0) / |S|)      when |S| > 0, else S as it is: anticge.py:68,74-76
+ * bm_anticge_sum: row_sq (DEVICE, h doubles) holds the squared norms where bm_row_sqnorms left them — the GLOBAL ones
+ *   under sharding, after the caller's all-reduce.  One workgroup ranks the rows; order_out (DEVICE, BM_MAX_ROWS int32,
+ *   may be NULL) receives the ranking (the h rows, then zeros) and scal_out[1] the squared norm of g_(maxpos) (+inf when
+ *   it is not finite).  One pass over the selected rows then writes S to sum_out (DEVICE, d floats, never an input) and
+ *   scal_out[0] = sum_j S_j^2 over the d coordinates given: this shard's part.  fp64 partial sums in a fixed order, no
+ *   float atomics, no synchronisation.  scal_out: DEVICE, 2 doubles.  ws: bm_anticge_workspace_bytes(d).
+ *   d == 0 is legal (an empty shard: scal_out[0] = 0).
+ * bm_anticge_scale: vec *= the multiplier above, in place, formed on the device from scal = { |S|^2, |g_(maxpos)|^2 }
+ *   (DEVICE; under sharding after the caller's all-reduce of scal[0]) with the reference's arithmetic: both norms
+ *   rounded to fp32 as `.norm().item()` returns them, nextafter and the quotient in double, ONE rounding to fp32
+ *   (`mul_` with a Python scalar).  A |S|^2 that is zero or NaN leaves vec untouched. */
+int64_t bm_anticge_workspace_bytes(int64_t d);
+int bm_anticge_sum(const float* const* rows, int h, int64_t d, int f_decl, const double* row_sq, float* sum_out,
+                   int32_t* order_out, double* scal_out, void* ws, void* stream);
+int bm_anticge_scale(float* vec, int64_t d, const double* scal, void* stream);
 
 /* y[i] = a*y[i] + b*x[i] for k vectors at once: worker momentum
  * `gmtm.mul_(mu).add_(grad, alpha=1-damp)` at attack.py:800-804. */
