@@ -39,6 +39,7 @@ OUT3_SUMS, OUT3_MAX = slice(0, 2), slice(2, 3)  # bm_stack_stats: sum avg^2, sum
 STEP_S2, STEP_SD, STEP_H2, STEP_HD, STEP_D2, STEP_A2, STEP_AD, STEP_L2 = range(8)
 STEP_GRAM, STEP_EX = slice(8, 24), slice(24, 26)
 STEP_SMAX, STEP_HMAX, STEP_DMAX, STEP_AMAX = range(26, 30)
+STEP_ACCEPT = 30  # krum: Byzantine rows among the m averaged (an integer; the same on every rank, reduced as a maximum)
 RANK_KRUM, RANK_BULYAN = 0, 1
 ATTACK_EMPIRE, ATTACK_LITTLE, ATTACK_DIRECTION = 0, 1, 16
 
@@ -81,6 +82,8 @@ SIGNATURES = {
                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
   "bm_sharded_sq_slot": (ctypes.c_void_p, [ctypes.c_void_p]),
   "bm_sharded_pair_workspace": (ctypes.c_void_p, [ctypes.c_void_p]),
+  "bm_sharded_order_slot": (ctypes.c_void_p, [ctypes.c_void_p]),
+  "bm_accept_count": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
   "bm_sharded_rule_from_sq": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _c_float_pp, ctypes.c_int, ctypes.c_int64,
                                              ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_void_p, ctypes.c_void_p]),

@@ -198,6 +198,10 @@ extern "C" int bm_sharded_bulyan(bm_comm* comm, const float* const* rows, int n,
 // (bm_sharded_sq_slot(ws), written by bm_momentum_stats_sqdist with ws_pair = bm_sharded_pair_workspace(ws)).
 extern "C" double* bm_sharded_sq_slot(void* ws) { return static_cast<double*>(ws); }
 extern "C" void* bm_sharded_pair_workspace(void* ws) { return static_cast<char*>(ws) + kShardHeader; }
+// where the three rules above leave their ranking (the acceptation count of a step reads it there: csrc/accept.hip)
+extern "C" int32_t* bm_sharded_order_slot(void* ws) {
+  return reinterpret_cast<int32_t*>(static_cast<char*>(ws) + BM_MAX_ROWS * BM_MAX_ROWS * 8);
+}
 
 extern "C" int bm_sharded_rule_from_sq(bm_comm* comm, int rule, const float* const* rows, int n, int64_t d_local, int f,
                                        int m, float* out_local, int32_t* order_out, void* ws, void* stream) {

@@ -16,6 +16,7 @@
 //            ||params - origin||^2 (:830), and the curvature combination C <- s + mu * (C - mu^(P-1) * oldest)
 //            for the next step (see step.py)
 //   pack     every scalar into one vector -> all-gather -> fixed-order sums / maxima -> stats_out
+//   accept   Krum: bm_accept_count on the ranking the rule left, one wavefront -> slot 30 of the same vector   :822
 #include "bm_common.h"
 
 namespace bm {
@@ -23,7 +24,9 @@ namespace bm {
 constexpr int kStatSums = 26;   // s2 sd h2 hd d2 a2 ad l2 | gram 4x4 | ex0 ex1
 constexpr int kStatMaxes = 4;   // smax hmax dmax amax
 constexpr int kStatSlots = 32;  // kStatSums + kStatMaxes, padded
-static_assert(kStatSums + kStatMaxes <= kStatSlots, "statistics vector layout");
+constexpr int kStatAccept = 30;  // Byzantine rows among the m Krum averaged: the same integer on every rank, so it lives
+                                 // among the maxima (the maximum over the ranks of one number is that number)
+static_assert(kStatSums + kStatMaxes <= kStatAccept && kStatAccept < kStatSlots, "statistics vector layout");
 
 // scratch scalars of one call, all fp64 on the device
 struct StepScalars {
@@ -214,6 +217,13 @@ extern "C" int bm_step_worker(bm_comm* comm, const bm_step_params* p, const floa
   hipLaunchKernelGGL(step_pack_kernel, dim3(1), dim3(64), 0, s, sc, fr > 0 ? 1 : 0, has_past ? 1 : 0, has_l2 ? 1 : 0,
                      comm == nullptr ? stats_out : static_cast<double*>(nullptr));
   BM_LAUNCH_CHECK();
+  // ---- the acceptation count (attack.py:822): the ranking is still where the rule left it, and the pack kernel has just
+  //      zeroed the slot — it stays 0 for every other rule ----
+  if (p->rule == BM_RULE_KRUM) {
+    rc = bm_accept_count(bm_sharded_order_slot(base + lay.ws_rule), m, h,
+                         (comm == nullptr ? stats_out : sc->mine) + kStatAccept, stream);
+    if (rc != 0) return rc;
+  }
   if (comm == nullptr) return 0;
   const int nranks = bm_comm_size(comm);
   if (nranks > BM_MAX_ROWS) return BM_EINVAL;

@@ -112,7 +112,8 @@ class HipBackend:
   # the optional legs step.AggregationStep plans with (read once, in its constructor); each names a method below
   capabilities = frozenset((
     "step_worker", "momentum_stats_colwise", "momentum_stats_sqdist", "stack_stats_colwise", "stack_stats_sqdist",
-    "device_search", "attack_ranking_device", "bulyan_pass2_eval", "order_pair", "colwise_eval", "sqdist2", "anticge"))
+    "device_search", "attack_ranking_device", "bulyan_pass2_eval", "order_pair", "colwise_eval", "sqdist2", "anticge",
+    "accept_count"))
 
   def __init__(self):
     from . import gars, stats
@@ -150,9 +151,11 @@ class HipBackend:
     """(sel, status) on the device; status -1 = no subset of n - f rows has a finite diameter (brute.py:68)."""
     return self.gars.brute_select_device(sq, n, f)
 
-  def sharded_rule(self, name, comm, gradients, f, m, d_total=None):
+  def sharded_rule(self, name, comm, gradients, f, m, d_total=None, with_order=False):
     """Multi-Krum / Bulyan of the local slice in one C call (bm_sharded_krum / bm_sharded_bulyan);
-    comm: NativeComm or None (one rank); d_total: length of the whole vectors (default: this shard's)."""
+    comm: NativeComm or None (one rank); d_total: length of the whole vectors (default: this shard's).
+    with_order: return (out, ranking) — the ranking where the call left it, a view of this stream's workspace
+    (bm_sharded_order_slot: no copy), valid on this stream until the next sharded rule reuses the workspace."""
     gars = self.gars
     n, d, device = gars._validate(gradients)
     lib = _lib.load()
@@ -163,6 +166,9 @@ class HipBackend:
     with torch.cuda.device(device):
       _lib.check(fn(comm.handle if comm is not None else None, _lib.pointer_table(gradients), n, d,
                     int(d_total) if d_total is not None else d, f, m, gars._ptr(out), None, gars._ptr(ws), gars._stream(device)), "bm_sharded_" + name)
+    if with_order:
+      at = lib.bm_sharded_order_slot(gars._ptr(ws)) - ws.data_ptr()
+      return out, ws[at:at + 4 * _lib.MAX_ROWS].view(torch.int32)
     return out
 
   def index_tensor(self, indices, like):
@@ -219,6 +225,10 @@ class HipBackend:
 
   def study_stats(self, *args, **kwargs):
     return self.stats.study_stats(*args, **kwargs)
+
+  def accept_count(self, order, count, h):
+    """Entries >= h among the first `count` of a device index table, as a device fp64[1] (stats.accept_count)."""
+    return self.stats.accept_count(order, count, h)
 
   def anticge(self, honests, f_decl, reduce):
     """The vector of the `anticge` attack on this device's slice of the honest gradients (stats.anticge_sum /
@@ -307,6 +317,11 @@ class ShardedAggregator:
         warnings.warn(f"libbm_gar RCCL communicator unavailable ({failure}); using torch.distributed collectives")
         self.single_call = False
     self.brute_status = None
+    # (index tensor, count): the rows the latest krum / rule_from_sq("krum") / brute / aksel / cge of THIS aggregator
+    # averaged are the first `count` entries of the tensor, which stays where the rule left it (device memory with the
+    # HIP backend; after a single-call krum a view of the stream's workspace: read it on that stream before the next
+    # sharded rule).  step.AggregationStep counts the Byzantine rows among them (attack.py:822)
+    self.last_selection = None
     self._total = None        # (length of the whole vectors, this rank's shard length when it was determined)
 
   def shard_rows(self, rows, d=None):
@@ -482,8 +497,12 @@ class ShardedAggregator:
     if m is None:
       m = n - f - 2
     if self.single_call:
-      return self.backend.sharded_rule("krum", self.native, local, f, m, self._total_of(local, d_total))
+      out, order = self.backend.sharded_rule("krum", self.native, local, f, m, self._total_of(local, d_total),
+                                             with_order=True)
+      self.last_selection = (order, m)
+      return out
     order = self.backend.rank(self.global_sqdist(local, d_total), n, f, m, _lib.RANK_KRUM)
+    self.last_selection = (order, m)
     return self.backend.selected_mean(local, order, m)
 
   def bulyan(self, local, f, m=None, d_total=None):
@@ -504,6 +523,7 @@ class ShardedAggregator:
     sq = self._all_reduce(local_sq)  # in place: a fresh tensor per call
     order = self.backend.rank(sq, n, f, m, _lib.RANK_KRUM if name == "krum" else _lib.RANK_BULYAN)
     if name == "krum":
+      self.last_selection = (order, m)
       return self.backend.selected_mean(local, order, m)
     return self.backend.bulyan_pass2(local, order, f, m)
 
@@ -512,7 +532,9 @@ class ShardedAggregator:
     count = (n + 1) // 2 if mode == "mid" else n - f
     sq = self.backend.aksel_sqdist(local)
     self._all_reduce(sq)
-    return self.backend.selected_mean(local, self.backend.argsort(sq, n), count)
+    order = self.backend.argsort(sq, n)
+    self.last_selection = (order, count)
+    return self.backend.selected_mean(local, order, count)
 
   def brute(self, local, f, d_total=None, check=False):
     """Brute rule: all-reduced distances, then the (deterministic) subset search on every rank — on the device with
@@ -535,10 +557,12 @@ class ShardedAggregator:
         elif code != 0:
           from . import gars
           raise RuntimeError(gars.BRUTE_NO_SUBSET)
+      self.last_selection = (sel, n - f)  # (after a host re-search: the subset that is averaged, not the device's)
       return self.backend.selected_mean(local, sel, n - f)
     self.brute_status = None
-    sel = self.backend.brute_select(sq.sqrt().cpu().contiguous(), n, f)
-    return self.backend.selected_mean(local, self.backend.index_tensor(sel, local[0]), n - f)
+    sel = self.backend.index_tensor(self.backend.brute_select(sq.sqrt().cpu().contiguous(), n, f), local[0])
+    self.last_selection = (sel, n - f)
+    return self.backend.selected_mean(local, sel, n - f)
 
   def check_brute(self):
     """Raise when the latest unchecked brute() of THIS aggregator had no usable answer (-1: the reference's assertion,
@@ -556,7 +580,9 @@ class ShardedAggregator:
     n = len(local)
     sq = self.backend.row_sqnorms(local)
     self._all_reduce(sq)
-    return self.backend.selected_mean(local, self.backend.argsort(sq, n), n - f)
+    order = self.backend.argsort(sq, n)
+    self.last_selection = (order, n - f)
+    return self.backend.selected_mean(local, order, n - f)
 
   def anticge(self, local_honests, f_decl, f_real):
     """The reference's `anticge` attack (attacks/anticge.py:49-78) on this rank's slice of the honest gradients:

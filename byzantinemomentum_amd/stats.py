@@ -17,7 +17,7 @@ from . import gars
 
 __all__ = ["compute_avg_dev_max", "stack_stats_async", "study_dots", "study_stats", "multi_axpby", "row_sqnorms", "momentum_stats", "momentum_stats_colwise", "momentum_stats_sqdist", "stack_stats_colwise", "stack_stats_sqdist",
            "multi_fma3", "clip_factors", "clip_factors_from_sq", "multi_scale", "clip_gradients", "l2_distance",
-           "step_worker", "anticge_sum", "anticge_scale", "anticge_attack"]
+           "step_worker", "anticge_sum", "anticge_scale", "anticge_attack", "accept_count"]
 
 _ptr = gars._ptr
 
@@ -328,6 +328,24 @@ def anticge_attack(grad_honests, f_decl, f_real, **kwargs):
     return [torch.full_like(grad_honests[0], math.nan)] * f_real
   byz, _, scal = anticge_sum(grad_honests, f_decl, row_sqnorms(grad_honests).contiguous())
   return [anticge_scale(byz, scal)] * f_real
+
+
+def accept_count(order, count, h):
+  """How many of the first `count` entries of `order` (DEVICE int32 row indices: the ranking or the subset a rule left)
+  are >= h, as a device fp64[1] tensor holding that integer (bm_accept_count, one wavefront).  With gradients = honests
+  + attacks and h honests it is the numerator of the rule's `influence` (attack.py:822).  No sync."""
+  if not (isinstance(order, torch.Tensor) and order.is_cuda and order.dtype == torch.int32 and order.dim() == 1
+          and order.is_contiguous()):
+    raise gars.GarInputError("accept_count: order must be a contiguous 1-D int32 tensor on a GPU")
+  if not 0 <= count <= min(_lib.MAX_ROWS, order.numel()) or h < 0:
+    raise gars.GarInputError(f"accept_count: count must be within 0..{min(_lib.MAX_ROWS, order.numel())} and h >= 0, "
+                             f"got count = {count}, h = {h}")
+  device = order.device
+  out = torch.empty(1, dtype=torch.float64, device=device)
+  with torch.cuda.device(device):
+    _lib.check(_lib.load().bm_accept_count(_ptr(order), int(count), int(h), _ptr(out), gars._stream(device)),
+               "bm_accept_count")
+  return out
 
 
 def multi_axpby(ys, xs, a, b):

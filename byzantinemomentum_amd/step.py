@@ -14,6 +14,8 @@ Given the sampled honest gradients of a step it performs, without leaving the GP
   4. the momentum of the update    server: M <- defense; update: M <- mu*M + (1-damp)*defense   attack.py:832-839
   5. the study statistics          sampled / honest / attack stacks, defense norm and max, six cosines,
                                    previous-step cosine and curvature, l2 distance from the origin   attack.py:828-868
+                                   and the attack acceptation ratio, `defense.influence(honests, attacks, f)`: of the rows
+                                   the rule averaged, the fraction that are Byzantine copies          attack.py:822
 With worker momentum, steps 0-2 and the sampled/honest statistics of step 5 are ONE kernel
 (bm_momentum_stats): every sampled gradient and every momentum buffer is read once.
 
@@ -26,6 +28,13 @@ attack.py hands to `model.update`.  Everything is asynchronous on the current st
 `floats()` fetches the scalars (one sync) — except for the factor search, sequential by nature: one
 synchronisation per evaluation, or ONE for the whole search when the rule is krum, brute or average
 (linesearch.py: every evaluation is then a function of (h+2)^2 scalars of one distance pass).
+
+The acceptation ratio (`floats()["accept_ratio"]`) costs no second ranking and no copy of its own: the rule left its
+selection in device memory (krum: the first m of the ranking; brute: the subset; aksel: the first c of the distance
+order; cge: the first n - f_decl of the norm order), ONE wavefront counts the entries >= h there (bm_accept_count;
+gradients = honests + [byz] * f_real), the integer travels with the scalars above and `floats()` divides it by the
+rule's denominator — the reference's own `int / int`.  average: f_real / n on the host; bulyan, median, trmean, phocas,
+meamed have no `influence` in the reference: the object math.nan.
 """
 
 import collections
@@ -56,11 +65,17 @@ class StepPlan(NamedTuple):
   device_cursor: bool     # the exploration's cursor (for Bulyan, the ranking too) lives in device memory
   single_call: bool       # run() is one bm_step_worker call
   capabilities: frozenset  # the optional legs the backend declared
+  accept: Optional[str] = None  # the acceptation ratio (attack.py:822): "count" = counted on the device from the rule's
+                                # selection (krum, brute, aksel, cge), "average" = f_real / n on the host, None = the rule
+                                # has no `influence` in the reference (math.nan)
 
 
 # every scalar of the study row, from the packed vector of bm_step_worker or from the exchange of the sequence
 # (gram: 4 x 4, row-major, of sampled avg, honest avg, defense, attack avg; ex0 / ex1: <s, newest past>, <s, C>)
-_StudyRecord = collections.namedtuple("_StudyRecord", "s2 sd smax h2 hd hmax a2 ad amax d2 dmax l2 gram ex0 ex1 prev_s2")
+# accept: Byzantine rows among those the rule averaged (an integer as a float; nan where nothing was counted)
+_StudyRecord = collections.namedtuple("_StudyRecord",
+                                      "s2 sd smax h2 hd hmax a2 ad amax d2 dmax l2 gram ex0 ex1 prev_s2 accept")
+_ACCEPT_COUNTED = ("krum", "brute", "aksel", "cge")  # the rules whose `influence` counts over a selection
 
 
 class AggregationStep:
@@ -181,7 +196,8 @@ class AggregationStep:
       search = "generic"
     single = bool(single_call and fixed and self.attack != "anticge" and self.momentum_at == "worker" and "step_worker" in caps
                   and gar in _DISTANCE + _COLWISE and only_m and (not self.agg.collective or self.agg.native is not None))
-    return StepPlan(only_m, analytic, first_pass, search, device_cursor, single, caps)
+    accept = "count" if gar in _ACCEPT_COUNTED else ("average" if gar == "average" else None)
+    return StepPlan(only_m, analytic, first_pass, search, device_cursor, single, caps, accept)
 
   # ------------------------------------------------------------------------ #
 
@@ -479,6 +495,8 @@ class AggregationStep:
       defense = agg.rule_from_sq(self.gar, honests + attacks, fused_sq, self.f_decl, self.gar_args.get("m"))
     else:
       defense = self._aggregate(honests + attacks)
+    # (attack.py:822) the Byzantine rows among those the rule has just averaged, counted where its selection is
+    accept, accept_of = self._accept_count() if self.plan.accept == "count" else (None, None)
     # 4. momentum of the update
     if self.momentum_at == "server":
       self.server_momentum = defense          # no clone, as attack.py:835
@@ -510,11 +528,21 @@ class AggregationStep:
                             **(dict(update_momentum=self.server_momentum, update_mu=self.mu, update_omd=omd)
                                if self.momentum_at == "update" else {}))
     self._pending = dict(s=s_out3, h=h_out3, study=study, npast=2 if count > 0 else 0,
-                         prev_s2=self._prev_s2 if count > 0 else None, has_l2=has_l2, ks=ks, floats=None)
+                         prev_s2=self._prev_s2 if count > 0 else None, has_l2=has_l2, ks=ks, floats=None, accept=accept,
+                         accept_of=accept_of)
     if self.nb_past > 0:
       self.pasts.appendleft(s_avg)
       self._prev_s2 = s_out3[:1]
     return defense
+
+  def _accept_count(self):
+    """(device fp64[1], denominator): how many of the rows the aggregator's latest rule averaged are Byzantine copies —
+    index >= h, gradients being honests + [byz] * f_real — and how many it averaged.  One wavefront where the backend
+    has the kernel, else plain torch on the index tensor, on its device; no synchronisation either way."""
+    order, count = self.agg.last_selection
+    if "accept_count" in self.plan.capabilities:
+      return self.ops.accept_count(order, count, self.h), count
+    return (order[:count] >= self.h).sum().to(torch.float64).reshape(1), count
 
   def _run_single_call(self, sampled, ks, omd, params, origin):
     h = self.h
@@ -533,7 +561,8 @@ class AggregationStep:
     self.last_byzantine = byz
     self._pending = dict(packed=stats, prev=self._prev_stats if count > 0 else None, npast=2 if count > 0 else 0,
                          has_l2=params is not None and origin is not None, ks=ks,
-                         floats=None)
+                         floats=None,  # (krum: slot STEP_ACCEPT of the packed vector counts over the m rows it averaged)
+                         accept_of=self.gar_args.get("m") or self.n - self.f_decl - 2)
     if self.nb_past > 0:
       self.pasts.appendleft(s_avg)
       self._prev_stats = stats
@@ -550,27 +579,29 @@ class AggregationStep:
     """One packed exchange of every scalar of the sequence (sums and maxima, all ranks), as a _StudyRecord."""
     s3, h3, st, prev = pend["s"], pend["h"], pend["study"], pend["prev_s2"]
     last = [prev] if prev is not None else []
+    acc = [pend["accept"]] if pend["accept"] is not None else []  # (every rank holds the same count: a maximum)
     if not self.agg.collective:
       # ONE copy to the host, ONE synchronisation: the whole tensors travel — three or four of them in one concatenation
       # — to be taken apart on the host (two `tolist()` were two copies with a host round trip between them: ~30 us of a
       # 0.95 ms step, profiles/r05_c_full_kernel_trace.csv; eight slices were two batched-copy launches)
-      flat = torch.cat([s3, h3, st] + last).tolist()
-      s3, h3, st, last = flat[0:3], flat[3:6], flat[6:6 + _lib.STUDY_SLOTS], flat[6 + _lib.STUDY_SLOTS:]
+      flat = torch.cat([s3, h3, st] + last + acc).tolist()
+      s3, h3, st, rest = flat[0:3], flat[3:6], flat[6:6 + _lib.STUDY_SLOTS], flat[6 + _lib.STUDY_SLOTS:]
+      last, acc = rest[:len(last)], rest[len(last):]
       sums = s3[_lib.OUT3_SUMS] + h3[_lib.OUT3_SUMS] + st[_lib.STUDY_SUMS] + st[_lib.STUDY_L2] + last
-      maxes = s3[_lib.OUT3_MAX] + h3[_lib.OUT3_MAX] + st[_lib.STUDY_MAXES]
+      maxes = s3[_lib.OUT3_MAX] + h3[_lib.OUT3_MAX] + st[_lib.STUDY_MAXES] + acc
     else:
       sums, maxes = self.agg.exchange(
         torch.cat([s3[_lib.OUT3_SUMS], h3[_lib.OUT3_SUMS], st[_lib.STUDY_SUMS], st[_lib.STUDY_L2]] + last),
-        torch.cat([s3[_lib.OUT3_MAX], h3[_lib.OUT3_MAX], st[_lib.STUDY_MAXES]]))
+        torch.cat([s3[_lib.OUT3_MAX], h3[_lib.OUT3_MAX], st[_lib.STUDY_MAXES]] + acc))
       ns = int(sums.numel())
       flat = torch.cat([sums, maxes]).tolist()
       sums, maxes = flat[:ns], flat[ns:]
     s2, sd, h2, hd = sums[0:4]
     st = sums[4:24]  # STUDY_SUMS: the slots of bm_study_stats keep their places
     gram, (ex0, ex1), (a2, ad) = st[_lib.STUDY_GRAM], st[_lib.STUDY_EX], st[_lib.STUDY_ATTACK]
-    smax, hmax, amax, dmax = maxes
+    smax, hmax, amax, dmax = maxes[:4]
     return _StudyRecord(s2, sd, smax, h2, hd, hmax, a2, ad, amax, gram[4 * 2 + 2], dmax, sums[24], gram, ex0, ex1,
-                        sums[25] if prev is not None else math.nan)
+                        sums[25] if prev is not None else math.nan, maxes[4] if acc else math.nan)
 
   @staticmethod
   def _unpack(pend):
@@ -581,7 +612,7 @@ class AggregationStep:
     return _StudyRecord(v[L.STEP_S2], v[L.STEP_SD], v[L.STEP_SMAX], v[L.STEP_H2], v[L.STEP_HD], v[L.STEP_HMAX],
                         v[L.STEP_A2], v[L.STEP_AD], v[L.STEP_AMAX], v[L.STEP_D2], v[L.STEP_DMAX], v[L.STEP_L2],
                         v[L.STEP_GRAM], v[L.STEP_EX.start], v[L.STEP_EX.start + 1],
-                        v[len(pend["packed"])] if pend["prev"] is not None else math.nan)
+                        v[len(pend["packed"])] if pend["prev"] is not None else math.nan, v[L.STEP_ACCEPT])
 
   def _study_floats(self, rec, pend):
     """The study row (attack.py:828-868) from the scalars of either path."""
@@ -598,6 +629,10 @@ class AggregationStep:
       return g[4 * i + j] / math.sqrt(g[5 * i]) / math.sqrt(g[5 * j])
 
     past = pend["npast"] > 0
+    if self.plan.accept == "count":  # the reference's own `count / m`, int / int (krum.py:144-151 and its likes)
+      accept = int(rec.accept) / pend["accept_of"]
+    else:  # math.nan ITSELF where the rule has no `influence`: two steps' dictionaries then compare equal
+      accept = self.f_real / self.n if self.plan.accept == "average" else nan
     return {
       "l2_origin": math.sqrt(rec.l2) if pend["has_l2"] else nan,
       "sampled_norm_avg": math.sqrt(rec.s2), "sampled_norm_dev": dev(rec.sd, k_s), "sampled_norm_max": rec.smax,
@@ -609,10 +644,11 @@ class AggregationStep:
       "cosin_splatt": cos(0, 3), "cosin_honatt": cos(1, 3), "cosin_attdef": cos(3, 2),
       "cosin_sampled": rec.ex0 / math.sqrt(rec.s2) / math.sqrt(rec.prev_s2) if past else nan,
       "curv_sampled": self.mu * rec.ex1 if past else nan,
+      "accept_ratio": accept,
     }
 
   def floats(self):
-    """Python floats of the study row (attack.py:828-868) for the last run(); synchronises once.
+    """Python floats of the study row (attack.py:822,828-868) for the last run(); synchronises once.
     Idempotent: a second call returns the same dictionary without touching the device."""
     pend = self._pending
     if pend is None:

@@ -358,6 +358,9 @@ int bm_sharded_bulyan(bm_comm* comm, const float* const* rows, int n, int64_t d_
  * bm_sharded_sq_slot(ws), using bm_sharded_pair_workspace(ws) as its ws_pair.  rule: BM_RULE_KRUM or BM_RULE_BULYAN. */
 double* bm_sharded_sq_slot(void* ws);
 void* bm_sharded_pair_workspace(void* ws);
+/* Where bm_sharded_krum / bm_sharded_bulyan / bm_sharded_rule_from_sq leave their ranking (DEVICE, BM_MAX_ROWS int32,
+ * inside ws): valid on the call's stream until the next of these calls with the same ws.  (Added within ABI 23.) */
+int32_t* bm_sharded_order_slot(void* ws);
 int bm_sharded_rule_from_sq(bm_comm* comm, int rule, const float* const* rows, int n, int64_t d_local, int f, int m,
                             float* out_local, int32_t* order_out, void* ws, void* stream);
 
@@ -374,6 +377,9 @@ int bm_sharded_rule_from_sq(bm_comm* comm, int rule, const float* const* rows, i
  *   [5] sum avg_a^2  [6] sum_i |a_i-avg_a|^2  [7] |params-origin|^2
  *   [8 + 4a + b] <core_a, core_b>, core = (sampled avg, honest avg, defense, attack avg)
  *   [24] <sampled avg, past_newest>  [25] <sampled avg, curv>   [26..29] max|avg_s|, max|avg_h|, max|defense|, max|avg_a|
+ *   [30] BM_RULE_KRUM: how many of the m rows the rule averaged are Byzantine copies (index >= n - f_real), an integer
+ *        (bm_accept_count on the rule's ranking; the "Attack acceptation ratio" of attack.py:822 is this over m);
+ *        0 for every other rule.  Every rank holds the same ranking: the slot is reduced as a maximum, not summed.
  * curv (in/out, may be NULL when nb_past = 0): C = sum_i mu^i past_i, updated for the NEXT step
  * (C <- s when past_count = 0, else C <- mu * (C + oldest_weight * past_oldest) ... see step.py);
  * past_oldest non-NULL only when the caller's ring of nb_past vectors is full (its last entry).
@@ -401,6 +407,16 @@ int bm_step_worker(bm_comm* comm, const bm_step_params* p, const float* const* s
                    float* sampled_avg_out, float* honest_avg_out, float* byz_out,
                    float* attack_avg_out, const float* past_newest, float* curv, const float* past_oldest,
                    const float* params, const float* origin, double* stats_out, void* ws, void* stream);
+
+/* The numerator of the "Attack acceptation ratio" (attack.py:571,822; krum.py:144-150, brute.py:132-140,
+ * aksel.py:97-105, cge.py:88-96) from the selection a rule left in device memory.  With gradients = honests + [byz] *
+ * f_real a selected row is an attack exactly when its index is >= h = n - f_real.
+ * order (DEVICE, at least `count` int32): row indices — a ranking of bm_krum_rank / bm_stable_argsort, or the subset of
+ * bm_brute_select_device.  out (DEVICE, 1 double): the number of entries >= h among the first `count`, an integer
+ * (count == 0 writes 0).  One wavefront on the caller's stream, no synchronisation; the caller divides by its
+ * denominator on the host, the reference's own `int / int`.  0 <= count <= BM_MAX_ROWS, h >= 0.
+ * (Added within ABI 23: a host recognises the leg by the presence of the symbol.) */
+int bm_accept_count(const int32_t* order, int count, int h, double* out, void* stream);
 
 /* ONE candidate of the attacks' factor search against the trimmed mean, phocas or meamed, evaluate only
  * (attacks/identical.py:73-76 with aggregators/trmean.py:69-109 as the defense):
