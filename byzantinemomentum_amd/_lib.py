@@ -109,6 +109,8 @@ SIGNATURES = {
   "bm_anticge_sum": (ctypes.c_int, [_c_float_pp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p,
                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
   "bm_anticge_scale": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+  "bm_attack_vector": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_float,
+                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
   "bm_multi_axpby": (ctypes.c_int, [_c_float_pp, _c_float_pp, ctypes.c_int, ctypes.c_int64,
                                     ctypes.c_float, ctypes.c_float, ctypes.c_void_p]),
   "bm_brute_select": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
@@ -190,6 +192,8 @@ class Search(ctypes.Structure):
               ("evaluations", ctypes.c_int32), ("awaiting", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+# bm_attack_vector_kind of include/bm_gar.h
+ATTACK_VECTOR_KINDS = {"nan": 0, "shift_one": 1, "shift_all": 2, "scale": 3}
 RULE_IDS = {"krum": 0, "bulyan": 1, "median": 2, "trmean": 3, "phocas": 4, "meamed": 5, "brute": 6, "average": 7}
 
 

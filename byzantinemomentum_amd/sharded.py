@@ -113,7 +113,7 @@ class HipBackend:
   capabilities = frozenset((
     "step_worker", "momentum_stats_colwise", "momentum_stats_sqdist", "stack_stats_colwise", "stack_stats_sqdist",
     "device_search", "attack_ranking_device", "bulyan_pass2_eval", "order_pair", "colwise_eval", "sqdist2", "anticge",
-    "accept_count"))
+    "accept_count", "attack_vector"))
 
   def __init__(self):
     from . import gars, stats
@@ -237,6 +237,9 @@ class HipBackend:
     reduce(scal[:1])
     return self.stats.anticge_scale(byz, scal)
 
+  def attack_vector(self, kind, h_avg, factor=None, target=None, want_direction=False):
+    return self.stats.attack_vector(kind, h_avg, factor, target, want_direction)
+
   def colwise_eval_supported(self, rule, n):
     return self.stats.colwise_eval_supported(rule, n)
 
@@ -288,6 +291,24 @@ def _anticge_scale_torch(vec, scal):
   if attnorm > 0:
     vec.mul_(-math.nextafter(byznorm, 0) / attnorm)
   return vec
+
+
+def _attack_vector_torch(kind, avg, factor, target, want_direction):
+  """bm_attack_vector in plain torch for a backend without the kernel: the same fp32 expression at every coordinate,
+  avg + factor * dir with dir in {0, 1} (never a copy of avg), the factor rounded to fp32 first."""
+  if kind == "nan":
+    return torch.full_like(avg, math.nan)
+  if isinstance(factor, torch.Tensor):  # (a device search's float64[1]: rounded as the kernel rounds it)
+    factor = factor.reshape(-1)[0].to(avg.device, torch.float32)
+  else:
+    factor = torch.tensor(float(factor), dtype=torch.float32, device=avg.device)
+  if kind == "scale":
+    return avg * factor
+  direction = torch.ones_like(avg) if kind == "shift_all" else torch.zeros_like(avg)
+  if kind == "shift_one" and target is not None and target >= 0:
+    direction[target] = 1
+  out = avg + factor * direction
+  return (out, direction) if want_direction else out
 
 
 class ShardedAggregator:
@@ -603,6 +624,34 @@ class ShardedAggregator:
     byz, _, scal = _anticge_sum_torch(self.backend, local, f_decl, self._all_reduce(self.backend.row_sqnorms(local)))
     self._all_reduce(scal[:1])
     return [_anticge_scale_torch(byz, scal)] * f_real
+
+  def attack_vector(self, kind, local_avg, factor=None, target_idx=None, d_total=None, want_direction=False):
+    """This rank's slice of the Byzantine vector of the `nan` / `bulyan` / `empire-strict` attacks from its slice of
+    the honest average (stats.attack_vector, bm_attack_vector): kind "nan", "shift_one" (avg + factor * e_target),
+    "shift_all" (avg + factor) or "scale" (avg * factor).  factor: a number, or a device float64 tensor.
+    target_idx ("shift_one"): a Python index into the WHOLE vector — negative ones count from its end, IndexError
+    outside [-d_total, d_total) as indexing raises in the reference.  The rank whose slice (shard_bounds) holds the
+    coordinate shifts it; every other rank is told "not here".  No collective — unless the total length is neither
+    stated nor carried by the shards (total_length).  want_direction ("shift_*"): returns (vector, direction).
+    A backend that declares the "attack_vector" capability runs the kernel; any other gets the same values in plain
+    torch."""
+    if kind not in _lib.ATTACK_VECTOR_KINDS:
+      raise ValueError(f"unknown attack vector kind {kind!r} (one of {sorted(_lib.ATTACK_VECTOR_KINDS)})")
+    if want_direction and kind not in ("shift_one", "shift_all"):
+      raise ValueError(f"kind {kind!r} has no direction vector")
+    target = None
+    if kind == "shift_one":
+      if not isinstance(target_idx, int) or isinstance(target_idx, bool):
+        raise ValueError(f"kind 'shift_one' needs an integer target_idx, got {target_idx!r}")
+      total = self.total_length(local_avg.numel(), d_total)
+      if not -total <= target_idx < total:
+        raise IndexError(f"index {target_idx} is out of bounds for dimension 0 with size {total}")
+      lo, hi = shard_bounds(total, self.world_size, self.rank)
+      where = target_idx % total
+      target = where - lo if lo <= where < hi else -1
+    if "attack_vector" in getattr(self.backend, "capabilities", ()):
+      return self.backend.attack_vector(kind, local_avg, factor, target, want_direction)
+    return _attack_vector_torch(kind, local_avg, factor, target, want_direction)
 
   def compute_avg_dev_max(self, local_samples):
     """Sharded tools.compute_avg_dev_max: (local slice of the average, norm, deviation, max)."""

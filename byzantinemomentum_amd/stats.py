@@ -17,7 +17,8 @@ from . import gars
 
 __all__ = ["compute_avg_dev_max", "stack_stats_async", "study_dots", "study_stats", "multi_axpby", "row_sqnorms", "momentum_stats", "momentum_stats_colwise", "momentum_stats_sqdist", "stack_stats_colwise", "stack_stats_sqdist",
            "multi_fma3", "clip_factors", "clip_factors_from_sq", "multi_scale", "clip_gradients", "l2_distance",
-           "step_worker", "anticge_sum", "anticge_scale", "anticge_attack", "accept_count"]
+           "step_worker", "anticge_sum", "anticge_scale", "anticge_attack", "accept_count",
+           "attack_vector", "nan_attack", "bulyan_attack", "empire_strict_attack"]
 
 _ptr = gars._ptr
 
@@ -328,6 +329,104 @@ def anticge_attack(grad_honests, f_decl, f_real, **kwargs):
     return [torch.full_like(grad_honests[0], math.nan)] * f_real
   byz, _, scal = anticge_sum(grad_honests, f_decl, row_sqnorms(grad_honests).contiguous())
   return [anticge_scale(byz, scal)] * f_real
+
+
+def attack_vector(kind, h_avg, factor=None, target=None, want_direction=False):
+  """The Byzantine vector of the `nan`, `bulyan` and `empire-strict` attacks from the honest average, one streaming pass
+  (bm_attack_vector): kind "nan" -> every coordinate NaN (attacks/nan.py:36-40; `h_avg` gives shape and device only),
+  "shift_one" -> h_avg + factor * e_target, "shift_all" -> h_avg + factor (attacks/identical.py:114-127,82-84),
+  "scale" -> h_avg * factor (attacks/empire.py:61-62 with factor = -epsilon).  factor: a number, or a DEVICE float64
+  tensor whose first element the kernel reads (as multi_fma3 takes it).  target ("shift_one"): a coordinate of THIS
+  tensor, or None / -1 when another rank holds it.  want_direction ("shift_*"): the 0 / 1 direction vector is stored by
+  the same launch; returns (vector, direction) then, else the vector — fresh tensors, `h_avg` untouched.  No sync."""
+  if kind not in _lib.ATTACK_VECTOR_KINDS:
+    raise gars.GarInputError(f"attack_vector: unknown kind {kind!r} (one of {sorted(_lib.ATTACK_VECTOR_KINDS)})")
+  _, d, device = gars._validate([h_avg])
+  shift = kind in ("shift_one", "shift_all")
+  if want_direction and not shift:
+    raise gars.GarInputError(f"attack_vector: kind {kind!r} has no direction vector to store")
+  if kind != "nan" and factor is None:
+    raise gars.GarInputError(f"attack_vector: kind {kind!r} needs a factor")
+  target = -1 if target is None or kind != "shift_one" else int(target)
+  if not -1 <= target < d:
+    raise gars.GarInputError(f"attack_vector: target must be a coordinate within [0, {d}) or -1, got {target}")
+  lib = _lib.load()
+  out = torch.empty_like(h_avg)
+  direction = torch.empty_like(h_avg) if want_direction else None
+  with torch.cuda.device(device):
+    if isinstance(factor, torch.Tensor):
+      _require_scalar_on(factor, device, "attack_vector: a tensor factor must be a contiguous float64 tensor on the vector's device")
+      host, dev = 0.0, _ptr(factor)
+    else:
+      host, dev = (0.0 if factor is None else float(factor)), None
+    _lib.check(lib.bm_attack_vector(_lib.ATTACK_VECTOR_KINDS[kind], _ptr(h_avg), d, target, ctypes.c_float(host), dev,
+                                    _ptr(out), _opt(direction), gars._stream(device)), "bm_attack_vector")
+  return (out, direction) if want_direction else out
+
+
+def _searched(grad_honests, avg, candidate, f_real, f_decl, defense, evals, kwargs):
+  """tools.line_maximize of |defense(honests + [candidate(x)] * f_real) - avg|^2 (attacks/identical.py:67-77,
+  attacks/empire.py:51-59): the generic search through the caller's rule, one synchronisation per evaluation."""
+  from . import linesearch
+  if not callable(defense):
+    raise gars.GarInputError(f"a searched attack needs the aggregation rule to defeat as `defense`, got {defense!r}")
+
+  def scape(x):
+    aggregated = defense(gradients=(grad_honests + [candidate(x)] * f_real), f=f_decl, model=kwargs.get("model"))
+    return sqdist2(aggregated, avg).item()
+  return linesearch.line_maximize(scape, evals=evals)[0]
+
+
+def nan_attack(grad_honests, f_real, **kwargs):
+  """Drop-in for the reference's `nan` attack (attacks/nan.py:24-40): `f_real` references to ONE new all-NaN tensor."""
+  grad_honests = list(grad_honests)
+  gars._validate(grad_honests)
+  if f_real <= 0:
+    return []
+  return [attack_vector("nan", grad_honests[0])] * f_real
+
+
+def bulyan_attack(grad_honests, f_real, f_decl=None, defense=None, factor=-16, negative=False, target_idx=-1, **kwargs):
+  """Drop-in for the reference's `bulyan` attack (attacks/identical.py:45-86,114-127): `f_real` references to ONE new
+  tensor avg + factor * dir, dir = all ones for target_idx "all", else one-hot at target_idx (a Python index, negative
+  ones count from the end).  factor > 0: fixed (negated by `negative`); factor < 0: searched within ceil(-factor)
+  evaluations of `defense(gradients=..., f=f_decl, model=...)`, `negative` flipping the candidates during the search
+  only, as the reference does.  The inputs are left untouched."""
+  grad_honests = list(grad_honests)
+  _, d, device = gars._validate(grad_honests)
+  if f_real <= 0:
+    return []
+  if target_idx == "all":
+    kind, target = "shift_all", None
+  else:
+    if not isinstance(target_idx, int) or isinstance(target_idx, bool):
+      raise gars.GarInputError(f"expected an integer or \"all\" for 'target_idx', got {target_idx!r}")
+    if not -d <= target_idx < d:
+      raise IndexError(f"index {target_idx} is out of bounds for dimension 0 with size {d}")
+    kind, target = "shift_one", target_idx % d
+  avg = stack_stats_async(grad_honests)[0]
+  if factor < 0:
+    sign = -1.0 if negative else 1.0
+    factor = _searched(grad_honests, avg, lambda x: attack_vector(kind, avg, sign * x, target), f_real, f_decl, defense,
+                       math.ceil(-factor), kwargs)
+  elif negative:
+    factor = -factor
+  return [attack_vector(kind, avg, factor, target)] * f_real
+
+
+def empire_strict_attack(grad_honests, f_real, f_decl=None, defense=None, epsilon=1, **kwargs):
+  """Drop-in for the reference's `empire-strict` attack (attacks/empire.py:29-64): `f_real` references to ONE new tensor
+  avg * (-epsilon).  epsilon > 0: fixed; epsilon < 0: searched within ceil(-epsilon) evaluations of
+  `defense(gradients=..., f=f_decl, model=...)`.  The inputs are left untouched."""
+  grad_honests = list(grad_honests)
+  gars._validate(grad_honests)
+  if f_real <= 0:
+    return []
+  avg = stack_stats_async(grad_honests)[0]
+  if epsilon < 0:
+    epsilon = _searched(grad_honests, avg, lambda x: attack_vector("scale", avg, -x), f_real, f_decl, defense,
+                        math.ceil(-epsilon), kwargs)
+  return [attack_vector("scale", avg, -epsilon)] * f_real
 
 
 def accept_count(order, count, h):

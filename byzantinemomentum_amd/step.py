@@ -10,6 +10,10 @@ Given the sampled honest gradients of a step it performs, without leaving the GP
                                    |GAR(honests + [avg_h + t*dir]*f) - avg_h|^2         attacks/identical.py:67-77
      or the "anticge" attack       byz = -(sum of the h - f_decl smallest honests), scaled to just below the next norm,
                                    repeated f_real times; no factor                     attacks/anticge.py:49-78
+     or "nan" / "hidden" / "empire-strict"  byz = all NaN | avg_h + factor*(ones or e_target) | avg_h*(-eps), ONE streaming
+                                   kernel behind the plain first pass (bm_attack_vector); "hidden" is the reference's
+                                   `bulyan` attack, factor and eps fixed or searched   attacks/nan.py:36-40,
+                                   attacks/identical.py:114-127, attacks/empire.py:46-64
   3. the aggregation rule          defense = GAR(honests + [byz]*f, f)                 attack.py:821
   4. the momentum of the update    server: M <- defense; update: M <- mu*M + (1-damp)*defense   attack.py:832-839
   5. the study statistics          sampled / honest / attack stacks, defense norm and max, six cosines,
@@ -50,6 +54,8 @@ __all__ = ["AggregationStep"]
 _RULES = ("krum", "bulyan", "median", "trmean", "phocas", "meamed", "aksel", "brute", "average", "cge")
 _COLWISE = ("median", "trmean", "phocas", "meamed")
 _DISTANCE = ("krum", "bulyan")
+_ATTACKS = ("empire", "little", "anticge", "nan", "hidden", "empire-strict")
+_VECTOR_ATTACKS = ("nan", "hidden", "empire-strict")  # formed by ShardedAggregator.attack_vector behind the first pass
 MAX_PAST = 4096  # past sampled averages kept for the curvature term (each is one d-vector of device memory)
 
 
@@ -61,6 +67,7 @@ class StepPlan(NamedTuple):
   analytic: bool          # line_search "auto" / "host": the search may use a rule's special form
   first_pass: str         # "rule" / "sqdist": the coordinate-wise rule / the distance pass of Krum, Bulyan rides along;
                           # "plain"; "direction": a factor search follows, the first pass forms the attack direction only
+                          # (searched "hidden" stays "plain": its direction comes from bm_attack_vector)
   search: Optional[str]   # None (fixed factor), "scalar_device", "scalar_host", "bulyan", "median", "colwise_eval", "generic"
   device_cursor: bool     # the exploration's cursor (for Bulyan, the ranking too) lives in device memory
   single_call: bool       # run() is one bm_step_worker call
@@ -82,7 +89,7 @@ class AggregationStep:
   def __init__(self, nb_workers, nb_decl_byz, nb_real_byz, gar="krum", gar_args=None, momentum=0.99,
                dampening=0.99, momentum_at="worker", attack="empire", attack_factor=1.1, nb_past=25,
                gradient_clip=None, aggregator=None, single_call=True, attack_evals=None, attack_negative=False,
-               line_search="auto"):
+               line_search="auto", attack_args=None):
     """aggregator: a sharded.ShardedAggregator (default: one over the default process group, or a
     single-rank one when torch.distributed is not initialised).
     single_call: with the HIP backend, worker-side momentum and a rule the C entry point knows
@@ -91,6 +98,13 @@ class AggregationStep:
     attack: "empire" / "little" (attacks/identical.py), or "anticge" (attacks/anticge.py: no factor — `attack_factor` is
     ignored, `attack_evals` must be None, and 1 <= nb_decl_byz <= honest workers); it runs as its own short chain behind
     the plain first pass (ShardedAggregator.anticge), with every momentum placement, clipping and rule.
+    "nan" (attacks/nan.py: no factor either, `attack_evals` must be None), "hidden" (the reference's `bulyan` attack,
+    attacks/identical.py:114-127 — "bulyan" names a rule here: factor, evaluations and `attack_negative` as for empire
+    and little; attack_args={"target_idx": int | "all"}, default -1, a Python index into the whole vector) and
+    "empire-strict" (attacks/empire.py: `attack_factor` is epsilon, a positive int, or `attack_evals` = E its
+    `epsilon:-E`; it has no `negative`) are one streaming kernel behind the plain first pass
+    (ShardedAggregator.attack_vector); never the single call.
+    attack_args: further arguments of the attack, for "hidden" alone.
     attack_evals: None = the fixed `attack_factor`; a positive integer E = the reference's `factor:-E` (its
     default is -16): the factor is searched each step with tools.line_maximize's exploration
     (identical.py:67-77), `attack_negative` being the attack's `negative` argument during the search.
@@ -104,9 +118,10 @@ class AggregationStep:
       raise ValueError(f"unknown aggregation rule {gar!r}")
     if momentum_at not in ("worker", "server", "update"):
       raise ValueError(f"momentum_at must be 'worker', 'server' or 'update', got {momentum_at!r}")
-    if attack not in ("empire", "little", "anticge"):
-      raise ValueError(f"unknown attack {attack!r} (empire: factor, little: factor, use a negative one for negative:True; "
-                       f"anticge: no factor)")
+    if attack not in _ATTACKS:
+      hint = "; the reference's `bulyan` attack is \"hidden\" here (bulyan names a rule)" if attack == "bulyan" else ""
+      raise ValueError(f"unknown attack {attack!r} (empire, little, hidden: factor, use a negative one for negative:True; "
+                       f"empire-strict: epsilon; anticge, nan: no factor){hint}")
     if attack_evals is not None and (not isinstance(attack_evals, int) or attack_evals < 1):
       raise ValueError(f"attack_evals must be a positive number of evaluations, got {attack_evals!r}")
     if attack == "anticge":
@@ -115,6 +130,21 @@ class AggregationStep:
       if nb_real_byz >= 1 and not 1 <= nb_decl_byz <= nb_workers - nb_real_byz:
         raise ValueError(f"the anticge attack needs 1 <= nb_decl_byz <= {nb_workers - nb_real_byz} honest workers "
                          f"(attacks/anticge.py:67-68 indexes the sorted norms at h - f_decl), got {nb_decl_byz}")
+    if attack_args is not None and (attack != "hidden" or not isinstance(attack_args, dict)
+                                    or set(attack_args) - {"target_idx"}):
+      raise ValueError(f"attack_args holds {{'target_idx': int | 'all'}} for the hidden attack and nothing else, "
+                       f"got {attack_args!r} with attack {attack!r}")
+    target_idx = (attack_args or {}).get("target_idx", -1)
+    if attack == "hidden" and target_idx != "all" and (not isinstance(target_idx, int) or isinstance(target_idx, bool)):
+      raise ValueError(f"target_idx must be an integer or \"all\" (attacks/identical.py:121-124), got {target_idx!r}")
+    if attack == "nan" and attack_evals is not None:
+      raise ValueError("the nan attack has no factor to search: attack_evals must be None")
+    if attack == "empire-strict":
+      if attack_negative:
+        raise ValueError("the empire-strict attack has no `negative` (attacks/empire.py:29): attack_negative must be False")
+      if attack_evals is None and (not isinstance(attack_factor, int) or isinstance(attack_factor, bool) or attack_factor < 1):
+        raise ValueError(f"the empire-strict attack takes a positive integer epsilon as attack_factor "
+                         f"(attacks/empire.py:82), got {attack_factor!r}")
     if line_search not in ("auto", "host", "generic"):
       raise ValueError(f"line_search must be 'auto', 'host' or 'generic', got {line_search!r}")
     if not 0 <= nb_past <= MAX_PAST:
@@ -134,6 +164,7 @@ class AggregationStep:
     self.damp = dampening
     self.momentum_at = momentum_at
     self.attack = attack
+    self.target_idx = target_idx
     self.factor = attack_factor
     self.clip = gradient_clip
     self.attack_evals = attack_evals
@@ -167,9 +198,11 @@ class AggregationStep:
     analytic = self.line_search in ("auto", "host")
     # the first pass: momentum_stats* (worker placement) and stack_stats* (update placement) make the same choice
     stem = {"worker": "momentum_stats_", "update": "stack_stats_"}.get(self.momentum_at)
-    if not fixed:
+    behind = self.attack == "anticge" or self.attack in _VECTOR_ATTACKS
+    strict = self.attack == "empire-strict"
+    if not fixed and self.attack != "hidden":  # (empire-strict: the empire direction, -avg)
       first_pass = "direction"
-    elif self.attack == "anticge":  # its own chain behind the plain first pass, which forms no attack vector
+    elif behind:  # a chain or a kernel of its own behind the plain first pass, which forms no attack vector
       first_pass = "plain"
     elif stem and k >= 1 and not self.gar_args and gar in _COLWISE and stem + "colwise" in caps:
       first_pass = "rule"
@@ -184,7 +217,8 @@ class AggregationStep:
     if fixed:
       search, device_cursor = None, False
     elif analytic and gar in linesearch.ANALYTIC_RULES and small and only_m:
-      device_cursor = self.line_search == "auto" and gar in getattr(self.ops, "device_search_rules", ())
+      # (the device form keeps its cursor inside the kernel: the abscissa 1 + x of empire-strict needs the host's)
+      device_cursor = self.line_search == "auto" and gar in getattr(self.ops, "device_search_rules", ()) and not strict
       search = "scalar_device" if device_cursor else "scalar_host"
     elif analytic and gar == "bulyan" and k >= 1 and small and only_m:
       search, device_cursor = "bulyan", device_cursor and "attack_ranking_device" in caps
@@ -194,7 +228,7 @@ class AggregationStep:
       search = "colwise_eval"
     else:
       search = "generic"
-    single = bool(single_call and fixed and self.attack != "anticge" and self.momentum_at == "worker" and "step_worker" in caps
+    single = bool(single_call and fixed and not behind and self.momentum_at == "worker" and "step_worker" in caps
                   and gar in _DISTANCE + _COLWISE and only_m and (not self.agg.collective or self.agg.native is not None))
     accept = "count" if gar in _ACCEPT_COUNTED else ("average" if gar == "average" else None)
     return StepPlan(only_m, analytic, first_pass, search, device_cursor, single, caps, accept)
@@ -269,20 +303,24 @@ class AggregationStep:
     """attacks/identical.py:67-77: the factor maximising |GAR(honests + [avg + t*dir]*f_real) - avg|^2 under
     the evaluation budget.  Like the reference, `negative` flips the sign of the candidates DURING the
     search only; the factor returned (and then applied) is the positive abscissa the search settled on.
-    Returns a number, or the device tensor whose [0] is the factor; sets last_search."""
+    Returns a number, or the device tensor whose [0] is the factor; sets last_search.
+    empire-strict (attacks/empire.py:51-59): `direction` is -avg and the candidate avg * (-x) is avg + (1 + x) * (-avg),
+    so every form is evaluated at the abscissa 1 + x of what the cursor proposes; the result is x, epsilon."""
     plan = self.plan
     if plan.search in ("scalar_device", "scalar_host"):
       return self._search_scalar(honests, h_avg, direction)
     on_device = plan.device_cursor and h_avg.is_cuda
     form = {"bulyan": self._bulyan_objective, "median": self._median_objective,
             "colwise_eval": self._colwise_objective, "generic": self._generic_objective}[plan.search]
-    return self._drive(form(honests, h_avg, direction, on_device), h_avg, on_device)
+    return self._drive(form(honests, h_avg, direction, on_device), h_avg, on_device,
+                       shift=1.0 if self.attack == "empire-strict" else 0.0)
 
-  def _drive(self, evaluate, h_avg, on_device):
+  def _drive(self, evaluate, h_avg, on_device, shift=0.0):
     """Run `evaluate(t) -> device fp64[1]` under the exploration of tools.line_maximize, its cursor in device memory
-    or on the host."""
+    or on the host.  shift: added to every proposal before it is evaluated (a number on the host, one small device
+    addition with a device cursor: no synchronisation); the trace and the result keep the cursor's own abscissae."""
     def objective(t):
-      sq = evaluate(t)
+      sq = evaluate(t + shift if shift else t)
       self.agg.all_reduce_sum(sq)
       return sq
 
@@ -316,6 +354,11 @@ class AggregationStep:
       found = self.last_search = self.ops.attack_search_device(sq, self.h, self.f_real, self.f_decl, self.gar, **args)
       return found
     ext = self._fetch(sq)  # the search's only synchronisation
+    if self.attack == "empire-strict":  # the exploration over the scalar objective at 1 + x
+      factor, self.last_search = linesearch.line_maximize(
+        lambda x: linesearch.attack_objective(ext, self.h, self.f_real, self.f_decl, self.gar, 1.0 + x, args["m"])[0],
+        evals=self.attack_evals)
+      return factor
     factor, self.last_search = linesearch.attack_line_search(ext, self.h, self.f_real, self.f_decl, self.gar, **args)
     return factor
 
@@ -427,9 +470,13 @@ class AggregationStep:
     # 1.+2. momentum, attack vector, sampled/honest statistics, in the form the plan chose for the first pass
     fused_defense, fused_sq = None, None
     first_pass = self.plan.first_pass
-    searched = first_pass == "direction"
+    searched = self.attack_evals is not None
+    with_direction = first_pass == "direction"
     anticge = self.attack == "anticge"
-    scale = None if anticge else (1.0 if searched else self.factor)  # None: the first pass forms no attack vector
+    vector, strict = self.attack in _VECTOR_ATTACKS, self.attack == "empire-strict"
+    kind = "empire" if strict else self.attack  # what the first pass forms (empire-strict searched: its direction)
+    # None: the first pass forms no attack vector
+    scale = None if anticge or (vector and not with_direction) else (1.0 if searched else self.factor)
     if self.momentum_at == "worker":
       if self.buffers is None:
         self.buffers = self._new_rows(h, sampled[0], zero=True)
@@ -442,8 +489,8 @@ class AggregationStep:
           sampled, self.buffers, self.mu, omd, factors, self.factor, self.attack, self.f_real,
           d_total=agg._total_of(sampled))
       else:  # ("direction": the attack direction alone; the Byzantine vector follows the factor search)
-        s_avg, h_avg, byz, out6 = ops.momentum_stats(sampled, self.buffers, self.mu, omd, factors, scale, self.attack,
-                                                     direction=searched)
+        s_avg, h_avg, byz, out6 = ops.momentum_stats(sampled, self.buffers, self.mu, omd, factors, scale, kind,
+                                                     direction=with_direction)
       honests = self.buffers
       s_out3, h_out3 = out6[:3], out6[3:]
     else:
@@ -469,7 +516,7 @@ class AggregationStep:
                                                           d_total=agg._total_of(sampled))
         h_out3 = o6[3:]
       else:
-        h_avg, h_out3, *byz = ops.stack_stats(honests, scale=scale, attack=self.attack, direction=searched)
+        h_avg, h_out3, *byz = ops.stack_stats(honests, scale=scale, attack=kind, direction=with_direction)
         byz = byz[0] if byz else None
       if self.momentum_at == "update" and ks == h:
         # the honest stack IS the sampled stack (attack.py:809-810): one pass gives both sets of statistics
@@ -480,12 +527,27 @@ class AggregationStep:
       # attacks/anticge.py:49-78 on the honest gradients the rule is about to see (the updated buffers under worker
       # placement): row norms, ranking, sum and scaling on the device, two small collectives under sharding
       byz = agg.anticge(honests, self.f_decl, self.f_real)[0]
+    if vector and self.f_real > 0:
+      # one streaming kernel on the honest average (bm_attack_vector); with a search, `hidden` takes its 0 / 1 direction
+      # from the same kernel at factor 1 and empire-strict waits for its epsilon
+      if self.attack == "nan":
+        byz = agg.attack_vector("nan", h_avg)
+      elif self.attack == "hidden":
+        where = dict(target_idx=self.target_idx, d_total=agg._total_of(sampled)) if self.target_idx != "all" else {}
+        made = agg.attack_vector("shift_all" if self.target_idx == "all" else "shift_one", h_avg,
+                                 1.0 if searched else self.factor, want_direction=searched, **where)
+        byz = made[1] if searched else made
+      elif not searched:
+        byz = agg.attack_vector("scale", h_avg, -self.factor)
     if searched and self.f_real > 0:
       direction = byz
       factor = self._search_factor(honests, h_avg, direction)  # a number, or the device search's tensor ([0]: the factor)
       self.last_factor = factor
-      byz = torch.empty_like(h_avg)  # grad_att.mul_(factor); byz_grad = grad_avg.add_(grad_att)  (identical.py:82-84)
-      ops.multi_fma3([byz], [h_avg], [direction], 1.0, factor)
+      if strict:  # byz_grad.mul_(-epsilon) with the epsilon found (empire.py:61-62)
+        byz = agg.attack_vector("scale", h_avg, -factor[:1] if isinstance(factor, torch.Tensor) else -factor)
+      else:
+        byz = torch.empty_like(h_avg)  # grad_att.mul_(factor); byz_grad = grad_avg.add_(grad_att)  (identical.py:82-84)
+        ops.multi_fma3([byz], [h_avg], [direction], 1.0, factor)
     attacks = [byz] * self.f_real
     self.last_byzantine = byz if self.f_real > 0 else None  # the Byzantine vector of this step (callers, tests)
     # 3. aggregation

@@ -220,6 +220,24 @@ int bm_anticge_sum(const float* const* rows, int h, int64_t d, int f_decl, const
                    int32_t* order_out, double* scal_out, void* ws, void* stream);
 int bm_anticge_scale(float* vec, int64_t d, const double* scal, void* stream);
 
+/* The Byzantine vector of the reference's `nan` (attacks/nan.py:36-40), `bulyan` (attacks/identical.py:114-127 with
+ * :82-84) and `empire-strict` (attacks/empire.py:61-62) attacks from the honest average, in ONE streaming pass.  This
+ * entry point joined ABI 23: an addition, no signature changed.
+ *   out[i] = NaN (bits 0x7FC00000) | avg[i] + factor*(i == target) | avg[i] + factor | avg[i]*factor
+ * every coordinate computed as written (avg + factor*dir with dir in {0, 1}, never a copy of avg: a -0.0 comes out as
+ * the reference's), in fp32.  The `bulyan` attack at a fixed factor: BM_AV_SHIFT_ONE / _ALL with its factor (negated
+ * by the caller for negative:True); `empire-strict`: BM_AV_SCALE with factor = -epsilon.
+ * factor_dev != NULL: the factor is read from DEVICE memory (a double, rounded to fp32 as bm_multi_fma3_bdev rounds
+ *   it) and `factor` is ignored.
+ * direction_out != NULL (SHIFT kinds only): the same launch also stores the 0/1 direction vector (d floats).
+ * target (BM_AV_SHIFT_ONE; any value of [-1, d) with the other kinds): a coordinate of THIS buffer in [0, d), or -1 =
+ *   not in this buffer (under sharding: a rank that does not hold the targeted coordinate).
+ * avg may be NULL for BM_AV_NAN only.  out must not overlap avg or direction_out.  d == 0 launches nothing.  No
+ * workspace, no atomics, no synchronisation. */
+enum bm_attack_vector_kind { BM_AV_NAN = 0, BM_AV_SHIFT_ONE = 1, BM_AV_SHIFT_ALL = 2, BM_AV_SCALE = 3 };
+int bm_attack_vector(int kind, const float* avg, int64_t d, int64_t target, float factor, const double* factor_dev,
+                     float* out, float* direction_out, void* stream);
+
 /* y[i] = a*y[i] + b*x[i] for k vectors at once: worker momentum
  * `gmtm.mul_(mu).add_(grad, alpha=1-damp)` at attack.py:800-804. */
 int bm_multi_axpby(float* const* y, const float* const* x, int k, int64_t d,
