@@ -493,8 +493,8 @@ def momentum_stats(sampled, buffers, mu, one_minus_damp, clip_factors_dev=None, 
 
 def momentum_stats_colwise(sampled, buffers, mu, one_minus_damp, clip_factors_dev, attack_scale, attack, rule, f, n_byz):
   """momentum_stats followed by a coordinate-wise rule over the updated buffers and `n_byz` copies of the Byzantine
-  vector — for the median / trimmed mean over 20 buffers and 1..6 copies INSIDE the same kernel
-  (bm_momentum_stats_colwise).  Returns (sampled_avg, honest_avg, byz, defense, out6). No sync."""
+  vector — for the four rules over 20 buffers and 5 copies, or 14 buffers and 11 copies, INSIDE the same kernel; any
+  other shape runs the two kernels, same results (bm_momentum_stats_colwise).  Returns (sampled_avg, honest_avg, byz, defense, out6). No sync."""
   ks, d, device = gars._validate(list(sampled))
   h = gars._validate(list(buffers) + [sampled[0]])[0] - 1
   if h < 1 or ks < h or n_byz < 1:
@@ -542,7 +542,7 @@ def momentum_stats_sqdist(sampled, buffers, mu, one_minus_damp, clip_factors_dev
 
 def stack_stats_colwise(rows, attack_scale, attack, rule, f, n_byz):
   """stack_stats (average, Byzantine vector, statistics) followed by a coordinate-wise rule over the rows and `n_byz`
-  copies of the Byzantine vector — ONE pass over the rows at k = 20 (1..6 copies) or 14 (11 copies)
+  copies of the Byzantine vector — ONE pass over the rows at k = 20 (5 copies) or 14 (11 copies)
   (bm_stack_stats_colwise: the honest rows of `--momentum-at update`).  Returns (avg, byz, defense, out6). No sync."""
   k, d, device = gars._validate(list(rows))
   if n_byz < 1:

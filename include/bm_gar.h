@@ -261,9 +261,9 @@ int bm_momentum_stats(const float* const* sampled, int ks, float* const* buffers
 /* The same first pass followed by a coordinate-wise rule over the h updated buffers and n_byz copies of byz_out, i.e.
  * defense_out = GAR(honests + [byz] * n_byz, f = rule_f) of attack.py:821 for rule_op = BM_OP_MEDIAN / TRMEAN / PHOCAS /
  * MEAMED (aggregators/median.py:39, trmean.py:33,81-109), with the results of bm_momentum_stats + bm_colwise (same
- * bits).  For the four rules over ks = h = 20 buffers and 1..6 Byzantine copies (n = 21..26: the
- * reference's n = 25, f = 5 among them), or 14 buffers and 11 copies (its n = 25, f = 11), the rule runs INSIDE the first pass, on the values it already holds in
- * registers: the rule's own pass over the n rows disappears (26 of the 97 row passes of such a step).  Any other
+ * bits).  For the four rules over ks = h = 20 buffers and 5 Byzantine copies (the reference's n = 25, f = 5), or 14
+ * buffers and 11 copies (its n = 25, f = 11), on 16-byte aligned rows, the rule runs INSIDE the first pass, on the
+ * values it already holds in registers: the rule's own pass over the n rows disappears (26 of the 97 row passes of such a step).  Any other
  * shape runs the two kernels one after the other.  byz_out and defense_out must be non-NULL, attack_kind without
  * BM_ATTACK_DIRECTION. */
 int bm_momentum_stats_colwise(const float* const* sampled, int ks, float* const* buffers, int h, int64_t d,
@@ -290,9 +290,10 @@ int bm_momentum_stats_sqdist(const float* const* sampled, int ks, float* const* 
  * Byzantine vector, statistics; tools/pytorch.py:97-125, attacks/identical.py:63-86) together with
  *   bm_stack_stats_colwise: defense_out = rule(rows + [byz] * n_byz, f = rule_f), the rule of bm_colwise;
  *   bm_stack_stats_sqdist : sq_nxn = the squared distances of rows + [byz] * n_byz (n = k + n_byz).
- * For k = 20 with 1..6 Byzantine copies, or 14 with 11, 16-byte aligned rows and d a multiple of 4 (for the distances
- * also: gradients long enough for the burst form) it is ONE pass over the k rows; otherwise the stand-alone kernels
- * run one after the other.  out6[0..2] = out6[3..5] = { sum avg^2, sum_i |row_i - avg|^2, max|avg| }. */
+ * For 16-byte aligned rows and d a multiple of 4 it is ONE pass over the k rows — bm_stack_stats_colwise at k = 20 with
+ * 5 Byzantine copies or 14 with 11 (the shapes of bm_momentum_stats_colwise), bm_stack_stats_sqdist at k = 20 with
+ * 1..6 copies or 14 with 11 and gradients long enough for the burst form; otherwise the stand-alone kernels run one
+ * after the other.  out6[0..2] = out6[3..5] = { sum avg^2, sum_i |row_i - avg|^2, max|avg| }. */
 int bm_stack_stats_colwise(const float* const* rows, int k, int64_t d, float* avg_out, float* byz_out, float scale,
                            int attack_kind, int rule_op, int rule_f, int n_byz, float* defense_out, double* out6,
                            void* ws, void* stream);

@@ -429,9 +429,9 @@ def test_rows_from_the_package_allocator(bm):
 def test_first_pass_with_the_rule_riding_along(bm):
   """bm_momentum_stats_colwise against bm_momentum_stats + bm_colwise on clones: same bits in the buffers, the two
   averages, the Byzantine vector, the six statistics and the aggregated vector — for the shapes with a fused
-  instance (ks = h = 20 with 1..6 Byzantine copies or 14 with 11; median / trmean / phocas / meamed, with and without
+  instance (ks = h = 20 with 5 Byzantine copies or 14 with 11; median / trmean / phocas / meamed, with and without
   clipping factors, NaN / inf columns, ragged tails) and for shapes that fall back to the two kernels (other row
-  counts, unaligned views)."""
+  counts, other numbers of copies — 20 + 1, 3, 6, 7 and 14 + 10 among them —, unaligned views)."""
   gen = torch.Generator(device=DEV).manual_seed(17)
   cases = [(20, 20, 5, "median", 0, 30011, 0, False), (20, 20, 5, "trmean", 5, 30011, 0, True),
            (20, 20, 1, "trmean", 3, 4099, 0, False), (20, 20, 6, "median", 0, 1 << 20, 0, True),
