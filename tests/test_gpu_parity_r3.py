@@ -321,7 +321,9 @@ def test_study_stats_burst_form_at_short_lengths():
 
 def test_study_stats_against_fp64(bm):
   """bm_study_stats alone, every curvature mode, with and without attack / l2, odd lengths and unaligned views:
-  every slot against fp64 torch, C against the same fp32 operations."""
+  every slot against fp64 torch, C against the same fp32 operations.  (Instance by instance — the momentum stream,
+  the attack-average output, the burst form's iteration counts, the fold of the plain form, C and M bit for bit —
+  in tests/test_gpu_study_matrix.py; the bars there are the ones below.)"""
   gen = torch.Generator(device=DEV).manual_seed(11)
   # (the two long ones reach the burst form when BM_STUDY_BURST=1 lowers its threshold to one iteration per CU:
   #  test_study_stats_burst_form_at_short_lengths; by default it starts at 8.4 M coordinates, the C5-size tests)
