@@ -26,10 +26,13 @@ def _graph(dist, n, t):
   return adj
 
 
-def _has_clique(adj, cand, need):
-  """The search tree of BruteWave::has_clique: forced removals, then the row with the most non-neighbours."""
+def _has_clique(adj, cand, need, count_nodes=None):
+  """The search tree of BruteWave::has_clique: forced removals, then the row with the most non-neighbours.
+  count_nodes: a one-element list that is incremented per node visited, the way the kernel counts `nodes`."""
   stack, have = [], True
   while True:
+    if count_nodes is not None:
+      count_nodes[0] += 1
     if not have:
       if not stack:
         return False
@@ -61,17 +64,37 @@ def _has_clique(adj, cand, need):
     have = True
 
 
-def parallel_search(dist, n, f, waves=W):
-  """(status, selection, rounds of phase 2, rounds of phase 3) as brute_select_kernel computes them."""
+PATHS = ("3a_only", "3b_rounds", "skipped_then_accepted", "shortcut_after_chosen", "row63_chosen")
+
+
+def parallel_search(dist, n, f, waves=W, trace=None):
+  """(status, selection, rounds of phase 2, rounds of phase 3) as brute_select_kernel computes them.
+
+  trace: a dict that receives what the search went through — "nodes": the search-tree nodes each wave visited (what
+  the kernel holds against its budget), "rounds3b": the rounds of phase 3b, "paths": which of PATHS the matrix reached
+  ("3b_rounds" from two rounds of 3b on)."""
   k = n - f
   everyone = (1 << n) - 1
+  nodes = [0] * waves
+  paths = set()
+  if trace is not None:
+    trace.update(nodes=nodes, rounds3b=0, paths=paths)
+
+  def ask(wave, adj, cand, need):
+    count = [0]
+    yes = _has_clique(adj, cand, need, count)
+    nodes[wave] += count[0]
+    return yes
+
   upper = [dist[i, j] for i in range(n) for j in range(i + 1, n)]  # row-major, pairs i < j
   finite = [v for v in upper if math.isfinite(v)]
   vmax = max([0.0] + finite)
-  if not _has_clique(_graph(dist, n, vmax), everyone, k):
+  feasible = ask(0, _graph(dist, n, vmax), everyone, k)
+  at_zero = ask(1, _graph(dist, n, 0.0), everyone, k)   # (wave 1 asks at the same time, whatever wave 0 finds)
+  if not feasible:
     return -1, None, 0, 0
   lo, hi, rounds = 0.0, vmax, 0
-  if _has_clique(_graph(dist, n, 0.0), everyone, k):
+  if at_zero:
     hi = 0.0
   else:
     while True:
@@ -84,7 +107,7 @@ def parallel_search(dist, n, f, waves=W):
       answers = []
       for w in range(askers):
         pivot = open_[((2 * w + 1) * total) // (2 * askers)]
-        answers.append((pivot, _has_clique(_graph(dist, n, pivot), everyone, k)))
+        answers.append((pivot, ask(w, _graph(dist, n, pivot), everyone, k)))
       for pivot, yes in answers:
         if yes and pivot < hi:
           hi = pivot
@@ -93,39 +116,64 @@ def parallel_search(dist, n, f, waves=W):
   adj = _graph(dist, n, hi)
   # 3a. the rows that lie in SOME set of k mutually adjacent rows (n independent questions, `waves` at a time): no other
   #     row can be chosen at any position, and when exactly k rows are left they are the answer
-  core = sum(1 << c for c in range(n) if _has_clique(adj, adj[c], k - 1))
+  core = sum(1 << c for c in range(n) if ask(c % waves, adj, adj[c], k - 1))
   rounds3 = -(-n // waves)
   if bin(core).count("1") == k:
+    paths.add("3a_only")
     return 0, [i for i in range(n) if core >> i & 1], rounds, rounds3
   # 3b. position by position among the rows of the core; a round tries the prefixes c_0, c_0 c_1, ... of the lowest
-  #     open rows (wave v assumes c_0 .. c_{v-1} chosen): the longest prefix that extends is taken whole, and the row
-  #     behind it has then failed exactly the question the sequential search would have asked
+  #     open rows (wave v assumes c_0 .. c_{v-1} chosen and asks whether c_v still extends; all waves ask at once): the
+  #     longest prefix of "yes" is taken whole, and the row behind it has then failed exactly the question the
+  #     sequential search would have asked
   cand, skipped, chosen, sel = core, 0, 0, []
   while chosen < k:
+    skipped &= cand
     open_rows = [i for i in range(n) if (cand & ~skipped) >> i & 1]
     if bin(cand).count("1") == k - chosen and skipped == 0:
       sel += [i for i in range(n) if cand >> i & 1]
+      if chosen > 0:
+        paths.add("shortcut_after_chosen")
       chosen = k
       break
     if not open_rows:
       return -1, None, rounds, rounds3
     rounds3 += 1
+    if trace is not None:
+      trace["rounds3b"] += 1
+      if trace["rounds3b"] >= 2:
+        paths.add("3b_rounds")
     tried = open_rows[:waves]
-    accepted, state = 0, cand
-    for v, c in enumerate(tried):
-      if chosen + v + 1 > k:
-        break
-      nxt = state & adj[c] & ~((1 << (c + 1)) - 1)
-      if not (state >> c & 1) or not _has_clique(adj, nxt, k - chosen - v - 1):  # (c must still be in play)
-        break  # (answers are monotone in v: the kernel takes the longest run of "yes" from v = 0)
-      state, accepted = nxt, v + 1
+    answers, states = [], []
+    for v in range(len(tried)):
+      state, in_play = cand, True
+      for c in tried[:v + 1]:
+        if not (state >> c & 1):
+          in_play = False  # (not adjacent to an earlier row of the prefix)
+        state = state & adj[c] & ~((1 << (c + 1)) - 1)
+      states.append(state)
+      answers.append(ask(v, adj, state, k - chosen - v - 1) if in_play and chosen + v + 1 <= k else None)
+    accepted = 0  # (answers are monotone in v: the kernel takes the longest run of "yes" from v = 0)
+    for v, yes in enumerate(answers):
+      if accepted == v and yes:
+        accepted += 1
     sel += tried[:accepted]
     chosen += accepted
     if accepted > 0:
-      cand, skipped = state, 0
+      if skipped:
+        paths.add("skipped_then_accepted")
+      if 63 in tried[:accepted]:
+        paths.add("row63_chosen")
+      cand, skipped = states[accepted - 1], 0
     if accepted < len(tried) and chosen < k:
       skipped |= 1 << tried[accepted]   # it failed with exactly the prefix the sequential search would have had
   return 0, sel, rounds, rounds3
+
+
+def search_paths(dist, n, f):
+  """(status, selection, paths reached, most search-tree nodes of any wave, rounds of 3b) of the model."""
+  trace = {}
+  status, sel, _, _ = parallel_search(dist, n, f, trace=trace)
+  return status, sel, trace["paths"], max(trace["nodes"]), trace["rounds3b"]
 
 
 def _lattice(rng, n, spread=6, bad_rows=0):

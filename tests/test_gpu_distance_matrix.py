@@ -185,6 +185,8 @@ def _rank_checks(bm, checks, case, fails, expect_listed):
     listed = D.listed_rows(rows)
     if bool(listed) != expect_listed:
       fails.append(f"{D.case_key(case)}: listed {listed}")
+    # (rank_from_sqdist runs the same rank_body.h: it is itself anchored, against a Python float64 reference and bit
+    #  for bit where the arithmetic is exact, by tests/test_gpu_selection_matrix.py)
     want_order, want_scores = bm.gars.rank_from_sqdist(sq, n, f, m, mode)
     if not torch.equal(order[:n], want_order[:n]) or not D.same_bits64(scores[:n], want_scores[:n]):
       fails.append(f"{D.case_key(case)} mode {mode}: not the ranking of the returned matrix")
