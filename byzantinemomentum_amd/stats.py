@@ -618,8 +618,9 @@ def attack_search_device(ext, h, k, f, rule, evals=16, negative=False, m=None):
   if not isinstance(evals, int) or evals < 1:
     _lib.check(_lib.EINVAL, "attack_search_device (evals must be a positive integer)")
   lib = _lib.load()
-  # (BM_SEARCH_TRACE=1, measurement only: the kernel appends 24 phase timestamps per candidate behind the results)
-  extra = 24 * evals if os.environ.get("BM_SEARCH_TRACE", "") == "1" else 0
+  # (BM_SEARCH_TRACE=1, measurement only: the kernel appends 24 phase timestamps per candidate behind the results; the
+  # library looks at the value's first character, search_device.hip, so the room is made on the same predicate)
+  extra = 24 * evals if os.environ.get("BM_SEARCH_TRACE", "")[:1] == "1" else 0
   out = torch.zeros(1 + 2 * evals + extra, dtype=torch.float64, device=ext.device) if extra else \
       torch.empty(1 + 2 * evals, dtype=torch.float64, device=ext.device)
   with torch.cuda.device(ext.device):
