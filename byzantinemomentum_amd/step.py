@@ -1,6 +1,8 @@
 """One aggregation step of the simulation loop on the HIP path (mirror of attack.py:757-878).
 
-Given the sampled honest gradients of a step it performs, without leaving the GPU:
+Given the sampled honest gradients of a step it performs, without leaving the GPU (run() calls one method per step:
+0 _clip_factors, 1 _first_pass, 2 _byzantine, 3 _defense, 4 _update_momentum, 5 _study; what each attack needs of them
+is one row of the _ATTACK table, what the constructor's arguments decide is the StepPlan):
   0. gradient clipping             g_i <- g_i * clip/||g_i|| where ||g_i|| > clip   attack.py:776-779,791-794
   1. momentum, by placement        worker: buf_i <- mu*buf_i + (1-damp)*g_i            attack.py:800-804
                                    server: hon_i  = (1-damp)*g_i + mu*M                attack.py:805-808
@@ -42,8 +44,9 @@ meamed have no `influence` in the reference: the object math.nan.
 """
 
 import collections
+import dataclasses
 import math
-from typing import NamedTuple, Optional
+from typing import Any, NamedTuple, Optional
 
 import torch
 
@@ -54,15 +57,43 @@ __all__ = ["AggregationStep"]
 _RULES = ("krum", "bulyan", "median", "trmean", "phocas", "meamed", "aksel", "brute", "average", "cge")
 _COLWISE = ("median", "trmean", "phocas", "meamed")
 _DISTANCE = ("krum", "bulyan")
-_ATTACKS = ("empire", "little", "anticge", "nan", "hidden", "empire-strict")
-_VECTOR_ATTACKS = ("nan", "hidden", "empire-strict")  # formed by ShardedAggregator.attack_vector behind the first pass
 MAX_PAST = 4096  # past sampled averages kept for the curvature term (each is one d-vector of device memory)
+
+
+class _Attack(NamedTuple):
+  """What the step needs to know of an attack: one row of _ATTACK per name, read by the constructor, _make_plan, the
+  factor search and _byzantine — none of them compares names."""
+  formed: str               # who forms the vector: "first_pass" (in its kernel), or behind the PLAIN first pass "chain"
+                            # (ShardedAggregator.anticge) / "kernel" (ShardedAggregator.attack_vector)
+  kind: Optional[str]       # "kernel": the kind attack_vector is handed ("shift_one": "shift_all" with target_idx "all")
+  first_pass: str           # the attack the first pass is handed: what it forms, for empire-strict the direction it forms
+                            # for a search (a first pass that forms nothing is handed the name, unread)
+  factor: bool              # it has a factor, fixed (`attack_factor`) or searched: it takes `attack_evals`
+  negative: bool            # it has the reference's `negative`
+  args: frozenset           # the `attack_args` it accepts
+  direction: Optional[str]  # what a search moves along: "first_pass" = the first pass in its "direction" form,
+                            # "kernel" = the 0 / 1 vector attack_vector leaves at factor 1; None: nothing to search
+  shift: float              # added to every abscissa of a search (avg * (-x) is avg + (1 + x) * (-avg): empire.py:51-59)
+  apply: Optional[str]      # the found factor: "fma" = multi_fma3 along the direction (identical.py:82-84), "scale" =
+                            # attack_vector("scale", avg, -epsilon), the factor being a positive integer epsilon (empire.py:61-62)
+
+
+_ATTACK = {
+  "empire": _Attack("first_pass", None, "empire", True, True, frozenset(), "first_pass", 0.0, "fma"),
+  "little": _Attack("first_pass", None, "little", True, True, frozenset(), "first_pass", 0.0, "fma"),
+  "anticge": _Attack("chain", None, "anticge", False, True, frozenset(), None, 0.0, None),
+  "nan": _Attack("kernel", "nan", "nan", False, True, frozenset(), None, 0.0, None),
+  "hidden": _Attack("kernel", "shift_one", "hidden", True, True, frozenset({"target_idx"}), "kernel", 0.0, "fma"),
+  "empire-strict": _Attack("kernel", "scale", "empire", True, False, frozenset(), "first_pass", 1.0, "scale"),
+}
+_ATTACKS = tuple(_ATTACK)
 
 
 class StepPlan(NamedTuple):
   """The forms a step takes, decided ONCE from the constructor's arguments and the backend's `capabilities`
-  (AggregationStep._make_plan).  run() and _search_factor() read it; they add three run-time facts only, each where it
-  matters: ks == h (update placement), whether the vectors are on a GPU, and d (bulyan_pass2_eval_supported)."""
+  (AggregationStep._make_plan).  The stages of run() and _search_factor() read it; they add three run-time facts only,
+  each where it matters: ks == h (update placement), whether the vectors are on a GPU, and d
+  (bulyan_pass2_eval_supported).  The VALUE of a fixed factor is read from the step when it runs."""
   only_m: bool            # no argument of the rule but "m"
   analytic: bool          # line_search "auto" / "host": the search may use a rule's special form
   first_pass: str         # "rule" / "sqdist": the coordinate-wise rule / the distance pass of Krum, Bulyan rides along;
@@ -75,6 +106,11 @@ class StepPlan(NamedTuple):
   accept: Optional[str] = None  # the acceptation ratio (attack.py:822): "count" = counted on the device from the rule's
                                 # selection (krum, brute, aksel, cge), "average" = f_real / n on the host, None = the rule
                                 # has no `influence` in the reference (math.nan)
+  searches: bool = False        # a factor search runs each step: attack_evals, and somebody to attack (f_real >= 1)
+  forms_vector: bool = True     # the first pass forms an attack vector — the direction alone when first_pass is
+                                # "direction" — at scale 1 with attack_evals, else at the fixed factor; False: a chain or
+                                # a kernel behind it forms the vector
+  attack: Optional[_Attack] = None  # the row of _ATTACK
 
 
 # every scalar of the study row, from the packed vector of bm_step_worker or from the exchange of the sequence
@@ -83,6 +119,36 @@ class StepPlan(NamedTuple):
 _StudyRecord = collections.namedtuple("_StudyRecord",
                                       "s2 sd smax h2 hd hmax a2 ad amax d2 dmax l2 gram ex0 ex1 prev_s2 accept")
 _ACCEPT_COUNTED = ("krum", "brute", "aksel", "cge")  # the rules whose `influence` counts over a selection
+
+
+class _FirstPass(NamedTuple):
+  """What AggregationStep._first_pass leaves for the stages behind it."""
+  honests: list       # the rows the rule sees (worker placement: the momentum buffers)
+  s_avg: Any          # sampled / honest averages
+  h_avg: Any
+  byz: Any            # the attack vector, or its direction before a search; None where the first pass forms none
+  s_out3: Any         # device fp64[3] each: |avg|^2, sum of squared deviations, max |avg|
+  h_out3: Any
+  fused_defense: Any  # first pass "rule": the coordinate-wise rule's output
+  fused_sq: Any       # first pass "sqdist": the n x n squared distances of the rule's stack
+
+
+@dataclasses.dataclass
+class _Pending:
+  """What a run() leaves for floats(): the device scalars of the step, not yet fetched.  `packed` is set by the single
+  call (the statistics vector of bm_step_worker; `prev`: the previous step's), the fields from `s` on by the sequence."""
+  ks: int                     # sampled gradients of the step
+  npast: int                  # 2 when the dots with the past were formed
+  has_l2: bool
+  accept_of: Optional[int]    # the denominator of the acceptation ratio (rows the rule averaged)
+  packed: Any = None
+  prev: Any = None
+  s: Any = None               # out3 of the sampled and of the honest stack
+  h: Any = None
+  study: Any = None           # the slots of bm_study_stats
+  prev_s2: Any = None         # device fp64[1]: |newest past average|^2
+  accept: Any = None          # device fp64[1]: Byzantine rows among those the rule averaged
+  floats: Optional[dict] = None  # the study row, once fetched
 
 
 class AggregationStep:
@@ -124,27 +190,24 @@ class AggregationStep:
                        f"empire-strict: epsilon; anticge, nan: no factor){hint}")
     if attack_evals is not None and (not isinstance(attack_evals, int) or attack_evals < 1):
       raise ValueError(f"attack_evals must be a positive number of evaluations, got {attack_evals!r}")
-    if attack == "anticge":
-      if attack_evals is not None:
-        raise ValueError("the anticge attack has no factor to search: attack_evals must be None")
-      if nb_real_byz >= 1 and not 1 <= nb_decl_byz <= nb_workers - nb_real_byz:
-        raise ValueError(f"the anticge attack needs 1 <= nb_decl_byz <= {nb_workers - nb_real_byz} honest workers "
-                         f"(attacks/anticge.py:67-68 indexes the sorted norms at h - f_decl), got {nb_decl_byz}")
-    if attack_args is not None and (attack != "hidden" or not isinstance(attack_args, dict)
-                                    or set(attack_args) - {"target_idx"}):
+    att = _ATTACK[attack]
+    if not att.factor and attack_evals is not None:
+      raise ValueError(f"the {attack} attack has no factor to search: attack_evals must be None")
+    if att.formed == "chain" and nb_real_byz >= 1 and not 1 <= nb_decl_byz <= nb_workers - nb_real_byz:
+      raise ValueError(f"the anticge attack needs 1 <= nb_decl_byz <= {nb_workers - nb_real_byz} honest workers "
+                       f"(attacks/anticge.py:67-68 indexes the sorted norms at h - f_decl), got {nb_decl_byz}")
+    if attack_args is not None and (not att.args or not isinstance(attack_args, dict) or set(attack_args) - att.args):
       raise ValueError(f"attack_args holds {{'target_idx': int | 'all'}} for the hidden attack and nothing else, "
                        f"got {attack_args!r} with attack {attack!r}")
     target_idx = (attack_args or {}).get("target_idx", -1)
-    if attack == "hidden" and target_idx != "all" and (not isinstance(target_idx, int) or isinstance(target_idx, bool)):
+    if "target_idx" in att.args and target_idx != "all" and (not isinstance(target_idx, int) or isinstance(target_idx, bool)):
       raise ValueError(f"target_idx must be an integer or \"all\" (attacks/identical.py:121-124), got {target_idx!r}")
-    if attack == "nan" and attack_evals is not None:
-      raise ValueError("the nan attack has no factor to search: attack_evals must be None")
-    if attack == "empire-strict":
-      if attack_negative:
-        raise ValueError("the empire-strict attack has no `negative` (attacks/empire.py:29): attack_negative must be False")
-      if attack_evals is None and (not isinstance(attack_factor, int) or isinstance(attack_factor, bool) or attack_factor < 1):
-        raise ValueError(f"the empire-strict attack takes a positive integer epsilon as attack_factor "
-                         f"(attacks/empire.py:82), got {attack_factor!r}")
+    if attack_negative and not att.negative:
+      raise ValueError("the empire-strict attack has no `negative` (attacks/empire.py:29): attack_negative must be False")
+    if att.apply == "scale" and attack_evals is None and (not isinstance(attack_factor, int) or isinstance(attack_factor, bool)
+                                                         or attack_factor < 1):
+      raise ValueError(f"the empire-strict attack takes a positive integer epsilon as attack_factor "
+                       f"(attacks/empire.py:82), got {attack_factor!r}")
     if line_search not in ("auto", "host", "generic"):
       raise ValueError(f"line_search must be 'auto', 'host' or 'generic', got {line_search!r}")
     if not 0 <= nb_past <= MAX_PAST:
@@ -162,6 +225,7 @@ class AggregationStep:
     self.gar_args = dict(gar_args or {})
     self.mu = momentum
     self.damp = dampening
+    self.omd = 1.0 - dampening
     self.momentum_at = momentum_at
     self.attack = attack
     self.target_idx = target_idx
@@ -198,9 +262,9 @@ class AggregationStep:
     analytic = self.line_search in ("auto", "host")
     # the first pass: momentum_stats* (worker placement) and stack_stats* (update placement) make the same choice
     stem = {"worker": "momentum_stats_", "update": "stack_stats_"}.get(self.momentum_at)
-    behind = self.attack == "anticge" or self.attack in _VECTOR_ATTACKS
-    strict = self.attack == "empire-strict"
-    if not fixed and self.attack != "hidden":  # (empire-strict: the empire direction, -avg)
+    att = _ATTACK[self.attack]
+    behind = att.formed != "first_pass"
+    if not fixed and att.direction == "first_pass":  # (empire-strict: the empire direction, -avg)
       first_pass = "direction"
     elif behind:  # a chain or a kernel of its own behind the plain first pass, which forms no attack vector
       first_pass = "plain"
@@ -218,7 +282,7 @@ class AggregationStep:
       search, device_cursor = None, False
     elif analytic and gar in linesearch.ANALYTIC_RULES and small and only_m:
       # (the device form keeps its cursor inside the kernel: the abscissa 1 + x of empire-strict needs the host's)
-      device_cursor = self.line_search == "auto" and gar in getattr(self.ops, "device_search_rules", ()) and not strict
+      device_cursor = self.line_search == "auto" and gar in getattr(self.ops, "device_search_rules", ()) and not att.shift
       search = "scalar_device" if device_cursor else "scalar_host"
     elif analytic and gar == "bulyan" and k >= 1 and small and only_m:
       search, device_cursor = "bulyan", device_cursor and "attack_ranking_device" in caps
@@ -231,7 +295,8 @@ class AggregationStep:
     single = bool(single_call and fixed and not behind and self.momentum_at == "worker" and "step_worker" in caps
                   and gar in _DISTANCE + _COLWISE and only_m and (not self.agg.collective or self.agg.native is not None))
     accept = "count" if gar in _ACCEPT_COUNTED else ("average" if gar == "average" else None)
-    return StepPlan(only_m, analytic, first_pass, search, device_cursor, single, caps, accept)
+    return StepPlan(only_m, analytic, first_pass, search, device_cursor, single, caps, accept,
+                    searches=not fixed and k > 0, forms_vector=not behind or first_pass == "direction", attack=att)
 
   # ------------------------------------------------------------------------ #
 
@@ -312,8 +377,7 @@ class AggregationStep:
     on_device = plan.device_cursor and h_avg.is_cuda
     form = {"bulyan": self._bulyan_objective, "median": self._median_objective,
             "colwise_eval": self._colwise_objective, "generic": self._generic_objective}[plan.search]
-    return self._drive(form(honests, h_avg, direction, on_device), h_avg, on_device,
-                       shift=1.0 if self.attack == "empire-strict" else 0.0)
+    return self._drive(form(honests, h_avg, direction, on_device), h_avg, on_device, shift=plan.attack.shift)
 
   def _drive(self, evaluate, h_avg, on_device, shift=0.0):
     """Run `evaluate(t) -> device fp64[1]` under the exploration of tools.line_maximize, its cursor in device memory
@@ -354,9 +418,10 @@ class AggregationStep:
       found = self.last_search = self.ops.attack_search_device(sq, self.h, self.f_real, self.f_decl, self.gar, **args)
       return found
     ext = self._fetch(sq)  # the search's only synchronisation
-    if self.attack == "empire-strict":  # the exploration over the scalar objective at 1 + x
+    shift = self.plan.attack.shift
+    if shift:  # the exploration over the scalar objective at 1 + x
       factor, self.last_search = linesearch.line_maximize(
-        lambda x: linesearch.attack_objective(ext, self.h, self.f_real, self.f_decl, self.gar, 1.0 + x, args["m"])[0],
+        lambda x: linesearch.attack_objective(ext, self.h, self.f_real, self.f_decl, self.gar, shift + x, args["m"])[0],
         evals=self.attack_evals)
       return factor
     factor, self.last_search = linesearch.attack_line_search(ext, self.h, self.f_real, self.f_decl, self.gar, **args)
@@ -450,131 +515,163 @@ class AggregationStep:
     """grad_sampleds: list of >= h flat fp32 GPU tensors (this rank's slice of the step's sampled
     gradients).  params/origin: optional flat parameter vectors for `l2_origin` (attack.py:830).
     Returns the aggregated gradient (slice); statistics stay on the device until floats()."""
-    ops, agg, h = self.ops, self.agg, self.h
     sampled = list(grad_sampleds)
     if getattr(grad_sampleds, "d_total", None) is not None:  # sharded.Shards: keep the stated total length
       from .sharded import Shards
       sampled = Shards(sampled, d_total=grad_sampleds.d_total)
-    ks = len(sampled)
-    if ks < h:
-      raise ValueError(f"{ks} sampled gradients for {h} honest workers")
-    omd = 1.0 - self.damp
+    if len(sampled) < self.h:
+      raise ValueError(f"{len(sampled)} sampled gradients for {self.h} honest workers")
     if self.single_call:
-      return self._run_single_call(sampled, ks, omd, params, origin)
-    # 0. clipping factors (device scalars; the all-reduce makes them global under sharding)
-    factors = None
-    if self.clip is not None:
-      sq = ops.row_sqnorms(sampled)
-      agg.all_reduce_sum(sq)
-      factors = ops.clip_factors_from_sq(sq, ks, self.clip)
-    # 1.+2. momentum, attack vector, sampled/honest statistics, in the form the plan chose for the first pass
-    fused_defense, fused_sq = None, None
-    first_pass = self.plan.first_pass
-    searched = self.attack_evals is not None
-    with_direction = first_pass == "direction"
-    anticge = self.attack == "anticge"
-    vector, strict = self.attack in _VECTOR_ATTACKS, self.attack == "empire-strict"
-    kind = "empire" if strict else self.attack  # what the first pass forms (empire-strict searched: its direction)
-    # None: the first pass forms no attack vector
-    scale = None if anticge or (vector and not with_direction) else (1.0 if searched else self.factor)
+      return self._run_single_call(sampled, len(sampled), self.omd, params, origin)
+    factors = self._clip_factors(sampled)                   # 0.
+    first = self._first_pass(sampled, factors)              # 1. and what it does of 2.
+    byz = self._byzantine(first, sampled)                   # 2.
+    defense = self._defense(first, [byz] * self.f_real)     # 3.
+    # (attack.py:822) the Byzantine rows among those the rule has just averaged, counted where its selection is
+    accept = self._accept_count() if self.plan.accept == "count" else (None, None)
+    self._update_momentum(defense)                          # 4.
+    self._study(first, defense, byz, params, origin, len(sampled), accept)  # 5.
+    return defense
+
+  def _clip_factors(self, sampled):
+    """Step 0 (attack.py:776-779,791-794): the clipping factors as device scalars, None without clipping; the all-reduce
+    makes the norms global under sharding."""
+    if self.clip is None:
+      return None
+    sq = self.ops.row_sqnorms(sampled)
+    self.agg.all_reduce_sum(sq)
+    return self.ops.clip_factors_from_sq(sq, len(sampled), self.clip)
+
+  def _first_pass(self, sampled, factors):
+    """Step 1 (attack.py:800-810) and what the first pass does of step 2: momentum by placement, the statistics of the
+    sampled and the honest stacks, and — in the form the plan chose — the attack vector or its direction
+    (attacks/identical.py:63-86,129-141), the coordinate-wise rule ("rule") or the rule's distance pass ("sqdist")."""
+    plan = self.plan
+    # None: the first pass forms no attack vector; with a search, the direction at factor 1
+    scale = (1.0 if plan.search is not None else self.factor) if plan.forms_vector else None
     if self.momentum_at == "worker":
-      if self.buffers is None:
-        self.buffers = self._new_rows(h, sampled[0], zero=True)
-      if first_pass == "rule":  # first pass + coordinate-wise rule in one call (one kernel for median / trmean at h = 20)
-        s_avg, h_avg, byz, fused_defense, out6 = ops.momentum_stats_colwise(
-          sampled, self.buffers, self.mu, omd, factors, self.factor, self.attack, self.gar, self.f_decl, self.f_real)
-      elif first_pass == "sqdist":
-        # first pass + the distance pass of the rule in one call (one kernel at h = 20 for long gradients)
-        s_avg, h_avg, byz, fused_sq, out6 = ops.momentum_stats_sqdist(
-          sampled, self.buffers, self.mu, omd, factors, self.factor, self.attack, self.f_real,
-          d_total=agg._total_of(sampled))
-      else:  # ("direction": the attack direction alone; the Byzantine vector follows the factor search)
-        s_avg, h_avg, byz, out6 = ops.momentum_stats(sampled, self.buffers, self.mu, omd, factors, scale, kind,
-                                                     direction=with_direction)
-      honests = self.buffers
-      s_out3, h_out3 = out6[:3], out6[3:]
+      return self._first_pass_worker(sampled, factors, scale)
+    return self._first_pass_stack(sampled, factors, scale)
+
+  def _first_pass_worker(self, sampled, factors, scale):
+    """buf_i <- mu*buf_i + (1-damp)*g_i (attack.py:800-804), clipping included, in ONE kernel with the statistics."""
+    ops, plan, att = self.ops, self.plan, self.plan.attack
+    fused_defense, fused_sq = None, None
+    if self.buffers is None:
+      self.buffers = self._new_rows(self.h, sampled[0], zero=True)
+    if plan.first_pass == "rule":  # first pass + coordinate-wise rule in one call (one kernel for median / trmean at h = 20)
+      s_avg, h_avg, byz, fused_defense, out6 = ops.momentum_stats_colwise(
+        sampled, self.buffers, self.mu, self.omd, factors, self.factor, att.first_pass, self.gar, self.f_decl, self.f_real)
+    elif plan.first_pass == "sqdist":
+      # first pass + the distance pass of the rule in one call (one kernel at h = 20 for long gradients)
+      s_avg, h_avg, byz, fused_sq, out6 = ops.momentum_stats_sqdist(
+        sampled, self.buffers, self.mu, self.omd, factors, self.factor, att.first_pass, self.f_real,
+        d_total=self.agg._total_of(sampled))
+    else:  # ("direction": the attack direction alone; the Byzantine vector follows the factor search)
+      s_avg, h_avg, byz, out6 = ops.momentum_stats(sampled, self.buffers, self.mu, self.omd, factors, scale,
+                                                   att.first_pass, direction=plan.first_pass == "direction")
+    return _FirstPass(self.buffers, s_avg, h_avg, byz, out6[:3], out6[3:], fused_defense, fused_sq)
+
+  def _first_pass_stack(self, sampled, factors, scale):
+    """server: hon_i = (1-damp)*g_i + mu*M (attack.py:805-808); update / none: hon_i = g_i (attack.py:809-810)."""
+    ops, att, h, ks = self.ops, self.plan.attack, self.h, len(sampled)
+    first_pass, fused_defense, fused_sq = self.plan.first_pass, None, None
+    if factors is not None:
+      ops.multi_scale(sampled, factors)  # in place, like the reference's grad.mul_
+    if self.momentum_at == "server":
+      # (first step: grad_momentum_server is zero, attack.py:678: hon_i = (1-damp)*g_i)
+      mom = self.server_momentum if self.server_momentum is not None else torch.zeros_like(sampled[0])
+      honests = self._new_rows(h, sampled[0])
+      ops.multi_fma3(honests, sampled[:h], [mom] * h, self.omd, self.mu)
     else:
-      if factors is not None:
-        ops.multi_scale(sampled, factors)  # in place, like the reference's grad.mul_
-      if self.momentum_at == "server":
-        # (first step: grad_momentum_server is zero, attack.py:678: hon_i = (1-damp)*g_i)
-        mom = self.server_momentum if self.server_momentum is not None else torch.zeros_like(sampled[0])
-        honests = self._new_rows(h, sampled[0])
-        ops.multi_fma3(honests, sampled[:h], [mom] * h, omd, self.mu)
-      else:
-        honests = sampled[:h]
-      # momentum at the update with every sampled gradient honest: the rule, or its distance pass, is fed from the pass
-      # that forms the statistics and the Byzantine vector (one pass over the rows at h = 20 / 14)
-      if ks != h and first_pass in ("rule", "sqdist"):
-        first_pass = "plain"
-      if first_pass == "rule":
-        h_avg, byz, fused_defense, o6 = ops.stack_stats_colwise(honests, self.factor, self.attack, self.gar, self.f_decl,
-                                                                self.f_real)
-        h_out3 = o6[3:]
-      elif first_pass == "sqdist":
-        h_avg, byz, fused_sq, o6 = ops.stack_stats_sqdist(honests, self.factor, self.attack, self.f_real,
-                                                          d_total=agg._total_of(sampled))
-        h_out3 = o6[3:]
-      else:
-        h_avg, h_out3, *byz = ops.stack_stats(honests, scale=scale, attack=kind, direction=with_direction)
-        byz = byz[0] if byz else None
-      if self.momentum_at == "update" and ks == h:
-        # the honest stack IS the sampled stack (attack.py:809-810): one pass gives both sets of statistics
-        s_avg, s_out3 = h_avg, h_out3
-      else:
-        s_avg, s_out3 = ops.stack_stats(sampled)
-    if anticge and self.f_real > 0:
+      honests = sampled[:h]
+    # momentum at the update with every sampled gradient honest: the rule, or its distance pass, is fed from the pass
+    # that forms the statistics and the Byzantine vector (one pass over the rows at h = 20 / 14)
+    if ks != h and first_pass in ("rule", "sqdist"):
+      first_pass = "plain"
+    if first_pass == "rule":
+      h_avg, byz, fused_defense, o6 = ops.stack_stats_colwise(honests, self.factor, att.first_pass, self.gar, self.f_decl,
+                                                              self.f_real)
+      h_out3 = o6[3:]
+    elif first_pass == "sqdist":
+      h_avg, byz, fused_sq, o6 = ops.stack_stats_sqdist(honests, self.factor, att.first_pass, self.f_real,
+                                                        d_total=self.agg._total_of(sampled))
+      h_out3 = o6[3:]
+    else:
+      h_avg, h_out3, *byz = ops.stack_stats(honests, scale=scale, attack=att.first_pass,
+                                            direction=first_pass == "direction")
+      byz = byz[0] if byz else None
+    if self.momentum_at == "update" and ks == h:
+      # the honest stack IS the sampled stack (attack.py:809-810): one pass gives both sets of statistics
+      s_avg, s_out3 = h_avg, h_out3
+    else:
+      s_avg, s_out3 = ops.stack_stats(sampled)
+    return _FirstPass(honests, s_avg, h_avg, byz, s_out3, h_out3, fused_defense, fused_sq)
+
+  def _byzantine(self, first, sampled):
+    """The rest of step 2: the chain or the kernel behind the plain first pass, the factor search and the found factor
+    applied.  Returns the Byzantine vector (the rule sees f_real references to it); sets last_byzantine, and with a
+    search last_factor / last_search."""
+    agg, plan, att = self.agg, self.plan, self.plan.attack
+    honests, h_avg, byz = first.honests, first.h_avg, first.byz
+    searched = plan.search is not None
+    if att.formed == "chain" and self.f_real > 0:
       # attacks/anticge.py:49-78 on the honest gradients the rule is about to see (the updated buffers under worker
       # placement): row norms, ranking, sum and scaling on the device, two small collectives under sharding
       byz = agg.anticge(honests, self.f_decl, self.f_real)[0]
-    if vector and self.f_real > 0:
+    if att.formed == "kernel" and self.f_real > 0:
       # one streaming kernel on the honest average (bm_attack_vector); with a search, `hidden` takes its 0 / 1 direction
       # from the same kernel at factor 1 and empire-strict waits for its epsilon
-      if self.attack == "nan":
-        byz = agg.attack_vector("nan", h_avg)
-      elif self.attack == "hidden":
+      if not att.factor:  # attacks/nan.py:36-40
+        byz = agg.attack_vector(att.kind, h_avg)
+      elif att.direction == "kernel":  # attacks/identical.py:114-127
         where = dict(target_idx=self.target_idx, d_total=agg._total_of(sampled)) if self.target_idx != "all" else {}
-        made = agg.attack_vector("shift_all" if self.target_idx == "all" else "shift_one", h_avg,
+        made = agg.attack_vector("shift_all" if self.target_idx == "all" else att.kind, h_avg,
                                  1.0 if searched else self.factor, want_direction=searched, **where)
         byz = made[1] if searched else made
-      elif not searched:
-        byz = agg.attack_vector("scale", h_avg, -self.factor)
-    if searched and self.f_real > 0:
+      elif not searched:  # attacks/empire.py:61-62 at the fixed epsilon
+        byz = agg.attack_vector(att.kind, h_avg, -self.factor)
+    if plan.searches:
       direction = byz
       factor = self._search_factor(honests, h_avg, direction)  # a number, or the device search's tensor ([0]: the factor)
       self.last_factor = factor
-      if strict:  # byz_grad.mul_(-epsilon) with the epsilon found (empire.py:61-62)
+      if att.apply == "scale":  # byz_grad.mul_(-epsilon) with the epsilon found (empire.py:61-62)
         byz = agg.attack_vector("scale", h_avg, -factor[:1] if isinstance(factor, torch.Tensor) else -factor)
       else:
         byz = torch.empty_like(h_avg)  # grad_att.mul_(factor); byz_grad = grad_avg.add_(grad_att)  (identical.py:82-84)
-        ops.multi_fma3([byz], [h_avg], [direction], 1.0, factor)
-    attacks = [byz] * self.f_real
+        self.ops.multi_fma3([byz], [h_avg], [direction], 1.0, factor)
     self.last_byzantine = byz if self.f_real > 0 else None  # the Byzantine vector of this step (callers, tests)
-    # 3. aggregation
-    if fused_defense is not None:
-      defense = fused_defense
-    elif fused_sq is not None:
-      defense = agg.rule_from_sq(self.gar, honests + attacks, fused_sq, self.f_decl, self.gar_args.get("m"))
-    else:
-      defense = self._aggregate(honests + attacks)
-    # (attack.py:822) the Byzantine rows among those the rule has just averaged, counted where its selection is
-    accept, accept_of = self._accept_count() if self.plan.accept == "count" else (None, None)
-    # 4. momentum of the update
+    return byz
+
+  def _defense(self, first, attacks):
+    """Step 3 (attack.py:821): what the first pass fused, the rule from the distances it left, or the rule itself."""
+    if first.fused_defense is not None:
+      return first.fused_defense
+    if first.fused_sq is not None:
+      return self.agg.rule_from_sq(self.gar, first.honests + attacks, first.fused_sq, self.f_decl, self.gar_args.get("m"))
+    return self._aggregate(first.honests + attacks)
+
+  def _update_momentum(self, defense):
+    """Step 4 (attack.py:832-839): what update_gradient() hands out."""
     if self.momentum_at == "server":
       self.server_momentum = defense          # no clone, as attack.py:835
       self._update = defense
     elif self.momentum_at == "update":
-      # M <- mu * M + (1 - damp) * defense (attack.py:836-838) rides along with the study block below, which reads the
-      # defense vector anyway (bm_study_stats_update): no pass of its own
+      # M <- mu * M + (1 - damp) * defense (attack.py:836-838) rides along with the study block, which reads the defense
+      # vector anyway (bm_study_stats_update): no pass of its own
       if self.server_momentum is None:
         self.server_momentum = torch.zeros_like(defense)
       self._update = self.server_momentum
     else:
       self._update = defense
-    # 5. remaining statistics, ONE pass over the vectors (bm_study_stats): attack stack, defense vector, the Gram
-    #    matrix behind the cosines, the dots with the past, l2 from the origin, and the curvature combination
-    #    for the next step.  grad_pasts.appendleft(PastGrad(sampled_grad_avg, sampled_norm_avg)) (attack.py:868)
-    #    happens every step, whether or not the scalars are fetched.
+
+  def _study(self, first, defense, byz, params, origin, ks, accept):
+    """Step 5 (attack.py:828-868): the remaining statistics in ONE pass over the vectors (bm_study_stats) — attack stack,
+    defense vector, the Gram matrix behind the cosines, the dots with the past, l2 from the origin, and the curvature
+    combination for the next step — left with the first pass's as the pending record of floats().
+    grad_pasts.appendleft(PastGrad(sampled_grad_avg, sampled_norm_avg)) (attack.py:868) happens every step, whether or
+    not the scalars are fetched."""
+    s_avg = first.s_avg
     count = len(self.pasts) if self.nb_past > 0 else 0
     mode = 0
     if self.nb_past > 0:
@@ -582,20 +679,18 @@ class AggregationStep:
         self._curv = torch.empty_like(s_avg)  # written by the first step (C <- s)
       mode = 1 if count == 0 else (3 if count == self.nb_past else 2)  # 3: the oldest entry leaves the deque
     has_l2 = params is not None and origin is not None
-    study = ops.study_stats(s_avg, h_avg, defense, byz if self.f_real > 0 else None, self.f_real,
-                            past_newest=self.pasts[0] if count > 0 else None, curv=self._curv,
-                            past_oldest=self.pasts[-1] if mode == 3 else None, curv_mode=mode, mu=self.mu,
-                            oldest_weight=-(self.mu ** (self.nb_past - 1)) if self.nb_past > 0 else 0.0,
-                            params=params if has_l2 else None, origin=origin if has_l2 else None,
-                            **(dict(update_momentum=self.server_momentum, update_mu=self.mu, update_omd=omd)
-                               if self.momentum_at == "update" else {}))
-    self._pending = dict(s=s_out3, h=h_out3, study=study, npast=2 if count > 0 else 0,
-                         prev_s2=self._prev_s2 if count > 0 else None, has_l2=has_l2, ks=ks, floats=None, accept=accept,
-                         accept_of=accept_of)
+    study = self.ops.study_stats(s_avg, first.h_avg, defense, byz if self.f_real > 0 else None, self.f_real,
+                                 past_newest=self.pasts[0] if count > 0 else None, curv=self._curv,
+                                 past_oldest=self.pasts[-1] if mode == 3 else None, curv_mode=mode, mu=self.mu,
+                                 oldest_weight=-(self.mu ** (self.nb_past - 1)) if self.nb_past > 0 else 0.0,
+                                 params=params if has_l2 else None, origin=origin if has_l2 else None,
+                                 **(dict(update_momentum=self.server_momentum, update_mu=self.mu, update_omd=self.omd)
+                                    if self.momentum_at == "update" else {}))
+    self._pending = _Pending(ks=ks, npast=2 if count > 0 else 0, has_l2=has_l2, accept_of=accept[1], s=first.s_out3,
+                             h=first.h_out3, study=study, prev_s2=self._prev_s2 if count > 0 else None, accept=accept[0])
     if self.nb_past > 0:
       self.pasts.appendleft(s_avg)
-      self._prev_s2 = s_out3[:1]
-    return defense
+      self._prev_s2 = first.s_out3[:1]
 
   def _accept_count(self):
     """(device fp64[1], denominator): how many of the rows the aggregator's latest rule averaged are Byzantine copies —
@@ -621,10 +716,10 @@ class AggregationStep:
       d_total=self.agg._total_of(sampled))
     self._update = defense
     self.last_byzantine = byz
-    self._pending = dict(packed=stats, prev=self._prev_stats if count > 0 else None, npast=2 if count > 0 else 0,
-                         has_l2=params is not None and origin is not None, ks=ks,
-                         floats=None,  # (krum: slot STEP_ACCEPT of the packed vector counts over the m rows it averaged)
-                         accept_of=self.gar_args.get("m") or self.n - self.f_decl - 2)
+    self._pending = _Pending(ks=ks, npast=2 if count > 0 else 0, has_l2=params is not None and origin is not None,
+                             # (krum: slot STEP_ACCEPT of the packed vector counts over the m rows it averaged)
+                             accept_of=self.gar_args.get("m") or self.n - self.f_decl - 2,
+                             packed=stats, prev=self._prev_stats if count > 0 else None)
     if self.nb_past > 0:
       self.pasts.appendleft(s_avg)
       self._prev_stats = stats
@@ -639,9 +734,9 @@ class AggregationStep:
 
   def _exchange(self, pend):
     """One packed exchange of every scalar of the sequence (sums and maxima, all ranks), as a _StudyRecord."""
-    s3, h3, st, prev = pend["s"], pend["h"], pend["study"], pend["prev_s2"]
+    s3, h3, st, prev = pend.s, pend.h, pend.study, pend.prev_s2
     last = [prev] if prev is not None else []
-    acc = [pend["accept"]] if pend["accept"] is not None else []  # (every rank holds the same count: a maximum)
+    acc = [pend.accept] if pend.accept is not None else []  # (every rank holds the same count: a maximum)
     if not self.agg.collective:
       # ONE copy to the host, ONE synchronisation: the whole tensors travel — three or four of them in one concatenation
       # — to be taken apart on the host (two `tolist()` were two copies with a host round trip between them: ~30 us of a
@@ -668,18 +763,18 @@ class AggregationStep:
   @staticmethod
   def _unpack(pend):
     """The statistics vector of bm_step_worker as a _StudyRecord."""
-    vec = pend["packed"] if pend["prev"] is None else torch.cat([pend["packed"], pend["prev"][:1]])
+    vec = pend.packed if pend.prev is None else torch.cat([pend.packed, pend.prev[:1]])
     v = vec.tolist()  # the only synchronisation
     L = _lib
     return _StudyRecord(v[L.STEP_S2], v[L.STEP_SD], v[L.STEP_SMAX], v[L.STEP_H2], v[L.STEP_HD], v[L.STEP_HMAX],
                         v[L.STEP_A2], v[L.STEP_AD], v[L.STEP_AMAX], v[L.STEP_D2], v[L.STEP_DMAX], v[L.STEP_L2],
                         v[L.STEP_GRAM], v[L.STEP_EX.start], v[L.STEP_EX.start + 1],
-                        v[len(pend["packed"])] if pend["prev"] is not None else math.nan, v[L.STEP_ACCEPT])
+                        v[len(pend.packed)] if pend.prev is not None else math.nan, v[L.STEP_ACCEPT])
 
   def _study_floats(self, rec, pend):
     """The study row (attack.py:828-868) from the scalars of either path."""
     nan = math.nan
-    att, k_s, k_h, k_a = self.f_real > 0, pend["ks"], self.h, self.f_real
+    att, k_s, k_h, k_a = self.f_real > 0, pend.ks, self.h, self.f_real
     g = rec.gram
 
     def dev(x, k):
@@ -690,13 +785,13 @@ class AggregationStep:
         return nan
       return g[4 * i + j] / math.sqrt(g[5 * i]) / math.sqrt(g[5 * j])
 
-    past = pend["npast"] > 0
+    past = pend.npast > 0
     if self.plan.accept == "count":  # the reference's own `count / m`, int / int (krum.py:144-151 and its likes)
-      accept = int(rec.accept) / pend["accept_of"]
+      accept = int(rec.accept) / pend.accept_of
     else:  # math.nan ITSELF where the rule has no `influence`: two steps' dictionaries then compare equal
       accept = self.f_real / self.n if self.plan.accept == "average" else nan
     return {
-      "l2_origin": math.sqrt(rec.l2) if pend["has_l2"] else nan,
+      "l2_origin": math.sqrt(rec.l2) if pend.has_l2 else nan,
       "sampled_norm_avg": math.sqrt(rec.s2), "sampled_norm_dev": dev(rec.sd, k_s), "sampled_norm_max": rec.smax,
       "honest_norm_avg": math.sqrt(rec.h2), "honest_norm_dev": dev(rec.hd, k_h), "honest_norm_max": rec.hmax,
       "attack_norm_avg": math.sqrt(rec.a2) if att else nan, "attack_norm_dev": dev(rec.ad, k_a) if att else nan,
@@ -715,8 +810,8 @@ class AggregationStep:
     pend = self._pending
     if pend is None:
       raise RuntimeError("floats() needs a run() first")
-    if pend["floats"] is None:
+    if pend.floats is None:
       if self.gar == "brute":
         self.agg.check_brute()  # (a step replayed from a HIP graph could not check inside run(): here at the latest)
-      pend["floats"] = self._study_floats(self._unpack(pend) if "packed" in pend else self._exchange(pend), pend)
-    return pend["floats"]
+      pend.floats = self._study_floats(self._unpack(pend) if pend.packed is not None else self._exchange(pend), pend)
+    return pend.floats

@@ -140,3 +140,116 @@ def test_a_device_search_hands_back_its_tensor_unread():
   assert step._search_factor(rows, rows[0], rows[1]) is found
   assert step._search_now is found
   assert step.last_search == [(1.0, 2.0), (1.5, 3.0)] and step.last_factor == 1.5
+
+
+# ---- the table of attacks (step._ATTACK) and the plan fields that replaced what run() derived every step ---- #
+
+EVERY_ATTACK = ("empire", "little", "anticge", "nan", "hidden", "empire-strict")
+
+
+def test_the_table_has_the_attacks_and_no_other():
+  from byzantinemomentum_amd import step
+  assert set(step._ATTACK) == set(step._ATTACKS) == set(EVERY_ATTACK) and len(step._ATTACK) == len(step._ATTACKS)
+  assert all(isinstance(row, step._Attack) for row in step._ATTACK.values())
+
+
+@pytest.mark.parametrize("backend", [EveryCapability, OracleBackend])
+@pytest.mark.parametrize("attack", EVERY_ATTACK)
+def test_plan_fields_are_the_expressions_run_computed(attack, backend):
+  """What run() derived from `self.attack` and `self.attack_evals` at every step before the plan stated it, written out
+  from those lines: `searched`, `with_direction`, `anticge`, `vector`, `strict`, `kind`, `scale is None`, and the
+  `behind` / `strict` of _make_plan and the `1 + x` of the two searches."""
+  from byzantinemomentum_amd import step
+  for evals in (None, 4):
+    if evals is not None and attack in ("anticge", "nan"):
+      with pytest.raises(ValueError, match="no factor to search"):
+        plan(backend, gar="krum", attack=attack, attack_evals=evals)
+      continue
+    for gar in EVERY_RULE:
+      for placement in ("worker", "server", "update"):
+        for f_real in (5, 0):
+          p = plan(backend, gar=gar, momentum_at=placement, attack=attack, attack_evals=evals, attack_factor=2,
+                   f_real=f_real)
+          tag = (attack, evals, gar, placement, f_real)
+          # run(), as it was
+          searched = evals is not None
+          with_direction = p.first_pass == "direction"
+          anticge = attack == "anticge"
+          vector, strict = attack in ("nan", "hidden", "empire-strict"), attack == "empire-strict"
+          kind = "empire" if strict else attack
+          scale_is_none = anticge or (vector and not with_direction)
+          assert p.searches is (searched and f_real > 0), tag              # `if searched and self.f_real > 0:`
+          assert (p.search is not None) is searched, tag                   # `1.0 if searched else self.factor`
+          assert p.forms_vector is (not scale_is_none), tag
+          assert p.attack.first_pass == kind, tag
+          assert with_direction is (searched and attack != "hidden"), tag  # _make_plan: `not fixed and attack != "hidden"`
+          # _make_plan: `behind`; the stages behind the first pass: `if anticge`, `if vector`, and below it "nan",
+          # "hidden", `elif not searched` (empire-strict); `if strict` where the found factor is applied
+          row = p.attack
+          assert row is step._ATTACK[attack], tag
+          assert (row.formed != "first_pass") is (anticge or vector), tag
+          assert (row.formed == "chain") is anticge and (row.formed == "kernel") is vector, tag
+          assert (row.formed == "kernel" and not row.factor) is (attack == "nan"), tag
+          assert (row.direction == "kernel") is (attack == "hidden"), tag
+          assert (row.apply == "scale") is strict, tag
+          assert row.kind == {"nan": "nan", "hidden": "shift_one", "empire-strict": "scale"}.get(attack), tag
+          # _search_factor / _search_scalar: `1.0 if self.attack == "empire-strict" else 0.0`, `1.0 + x`
+          assert row.shift == (1.0 if strict else 0.0), tag
+          # the constructor: who takes attack_evals, `negative`, attack_args
+          assert row.factor is (attack not in ("anticge", "nan")) and row.negative is (not strict), tag
+          assert row.args == ({"target_idx"} if attack == "hidden" else set()), tag
+
+
+UNKNOWN_ATTACK = ("unknown attack {!r} (empire, little, hidden: factor, use a negative one for negative:True; "
+                  "empire-strict: epsilon; anticge, nan: no factor)")
+ATTACK_ARGS = "attack_args holds {{'target_idx': int | 'all'}} for the hidden attack and nothing else, got {!r} with attack {!r}"
+TARGET_IDX = "target_idx must be an integer or \"all\" (attacks/identical.py:121-124), got {!r}"
+EPSILON = "the empire-strict attack takes a positive integer epsilon as attack_factor (attacks/empire.py:82), got {!r}"
+ANTICGE_DECL = ("the anticge attack needs 1 <= nb_decl_byz <= {} honest workers "
+                "(attacks/anticge.py:67-68 indexes the sorted norms at h - f_decl), got {}")
+REFUSALS = [
+  (dict(gar="nope"), "unknown aggregation rule 'nope'"),
+  (dict(momentum_at="client"), "momentum_at must be 'worker', 'server' or 'update', got 'client'"),
+  (dict(attack="bulyan"), UNKNOWN_ATTACK.format("bulyan")
+   + "; the reference's `bulyan` attack is \"hidden\" here (bulyan names a rule)"),
+  (dict(attack="empire_strict"), UNKNOWN_ATTACK.format("empire_strict")),
+  (dict(attack_evals=0), "attack_evals must be a positive number of evaluations, got 0"),
+  (dict(attack_evals=2.5), "attack_evals must be a positive number of evaluations, got 2.5"),
+  (dict(attack="hidden", attack_evals=-1), "attack_evals must be a positive number of evaluations, got -1"),
+  (dict(attack="anticge", attack_evals=4), "the anticge attack has no factor to search: attack_evals must be None"),
+  (dict(attack="nan", attack_evals=4), "the nan attack has no factor to search: attack_evals must be None"),
+  (dict(attack="anticge", f=0), ANTICGE_DECL.format(9, 0)),
+  (dict(attack="anticge", f=10), ANTICGE_DECL.format(9, 10)),
+  (dict(attack="hidden", attack_args={"target": 3}), ATTACK_ARGS.format({"target": 3}, "hidden")),
+  (dict(attack="hidden", attack_args={"target_idx": 3, "more": 1}), ATTACK_ARGS.format({"target_idx": 3, "more": 1}, "hidden")),
+  (dict(attack="hidden", attack_args=[3]), ATTACK_ARGS.format([3], "hidden")),
+] + [
+  (dict(attack=other, attack_factor=2, attack_args=given), ATTACK_ARGS.format(given, other))
+  for other in ("empire", "little", "anticge", "nan", "empire-strict") for given in ({"target_idx": 3}, {})
+] + [
+  (dict(attack="hidden", attack_args={"target_idx": bad}), TARGET_IDX.format(bad)) for bad in (1.5, "last", None, True)
+] + [
+  (dict(attack="empire-strict", attack_factor=2, attack_negative=True),
+   "the empire-strict attack has no `negative` (attacks/empire.py:29): attack_negative must be False"),
+] + [
+  (dict(attack="empire-strict", attack_factor=bad), EPSILON.format(bad)) for bad in (1.1, 2.0, 0, -3, True, None)
+] + [
+  (dict(line_search="device"), "line_search must be 'auto', 'host' or 'generic', got 'device'"),
+  (dict(nb_past=-1), "nb_past must be within 0..4096"),
+  (dict(nb_past=4097), "nb_past must be within 0..4096"),
+]
+
+
+def test_every_refusal_of_the_constructor_keeps_its_type_and_message():
+  agg = ShardedAggregator(backend=OracleBackend())
+  for kwargs, message in REFUSALS:
+    kwargs = dict(kwargs)
+    with pytest.raises(ValueError) as info:
+      AggregationStep(11, kwargs.pop("f", 2), 2, aggregator=agg, **kwargs)
+    assert type(info.value) is ValueError and str(info.value) == message, kwargs
+  # what is accepted next to them
+  for kwargs in (dict(attack="nan", attack_factor="ignored"), dict(attack="empire-strict", attack_factor=2),
+                 dict(attack="empire-strict", attack_evals=4), dict(attack="anticge", attack_negative=True),
+                 dict(attack="hidden", attack_args={"target_idx": "all"}, attack_evals=4, attack_negative=True)):
+    AggregationStep(11, 2, 2, aggregator=agg, **kwargs)
+  AggregationStep(11, 0, 0, aggregator=agg, attack="anticge")  # (nobody attacks: nb_decl_byz is not looked at)
