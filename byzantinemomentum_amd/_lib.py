@@ -42,6 +42,9 @@ STEP_SMAX, STEP_HMAX, STEP_DMAX, STEP_AMAX = range(26, 30)
 STEP_ACCEPT = 30  # krum: Byzantine rows among the m averaged (an integer; the same on every rank, reduced as a maximum)
 RANK_KRUM, RANK_BULYAN = 0, 1
 ATTACK_EMPIRE, ATTACK_LITTLE, ATTACK_DIRECTION = 0, 1, 16
+CENTER_GEOMED, CENTER_CCLIP = 0, 1  # bm_center_mode
+CENTER_MODES = {"geomed": CENTER_GEOMED, "cclip": CENTER_CCLIP}
+CENTER_MAX_ITERS = 64
 
 _c_float_pp = ctypes.POINTER(ctypes.c_void_p)
 
@@ -183,6 +186,13 @@ SIGNATURES = {
                                                   ctypes.c_void_p, ctypes.c_void_p]),
   "bm_attack_ranking": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                        ctypes.c_int, ctypes.c_double, ctypes.c_void_p]),
+  "bm_center_weights": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                       ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]),
+  "bm_center_weights_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                              ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p]),
+  "bm_weighted_sum": (ctypes.c_int, [_c_float_pp, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                     ctypes.c_void_p]),
 }
 
 class Search(ctypes.Structure):

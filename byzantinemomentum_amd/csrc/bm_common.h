@@ -302,6 +302,7 @@ struct Tuning {
   int rank_algo;       // BM_RANK_ALGO: how the rows' distances are put in order for the scores (rank_body.h): 0 (default) = counting up to 32 rows, a bitonic network per row beyond; 1 = bitonic, 2 = counting (A/B; same scores)
   int col_wide;        // BM_COL_WIDE: 1 (default) = median / trimmed mean at 29-52 rows take 16-byte columns, 0 = 8-byte ones (A/B)
   int brute_budget;    // BM_BRUTE_BUDGET: search-tree nodes per wave of the device Brute search before it gives up with status -2 (default 0 = 2^18; tests set a tiny one)
+  int wsum_piece;      // BM_WSUM_PIECE: columns per launch piece of bm_weighted_sum (default 0 = 2^29; tests set a small one to walk several pieces)
 };
 const Tuning& tuning();
 Tuning& tuning_mutable();  // bm_tuning_set (A/B runs inside one process)

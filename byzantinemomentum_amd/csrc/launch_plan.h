@@ -49,12 +49,13 @@ static inline void advance(T* (&table)[K], int64_t by) {
 }
 
 // The pieces of at most kMaxColsPerLaunch columns of a pass whose kernels address with 32-bit byte offsets:
-// piece(lo, count) for each, in order; the first non-zero code ends the walk.
+// piece(lo, count) for each, in order; the first non-zero code ends the walk.  (max_cols: a launch site whose tests walk
+// several pieces at a small d passes a smaller piece, never a larger one.)
 static inline int64_t piece_count(int64_t d) { return d > 0 ? (d + kMaxColsPerLaunch - 1) / kMaxColsPerLaunch : 0; }
 template <class Piece>
-static int for_pieces(int64_t d, Piece&& piece) {
-  for (int64_t lo = 0; lo < d; lo += kMaxColsPerLaunch) {
-    const int64_t count = (d - lo < kMaxColsPerLaunch) ? (d - lo) : kMaxColsPerLaunch;
+static int for_pieces(int64_t d, Piece&& piece, int64_t max_cols = kMaxColsPerLaunch) {
+  for (int64_t lo = 0; lo < d; lo += max_cols) {
+    const int64_t count = (d - lo < max_cols) ? (d - lo) : max_cols;
     if (const int rc = piece(lo, count)) return rc;
   }
   return 0;

@@ -23,7 +23,7 @@ from . import _lib
 __all__ = ["median", "trmean", "phocas", "meamed", "krum", "bulyan", "brute", "aksel", "average", "cge",
            "krum_selection", "bulyan_ranking", "brute_selection", "aksel_selection", "cge_selection",
            "pairwise_sqdist", "rank_from_sqdist", "selected_mean", "bulyan_pass2", "aksel_sqdist",
-           "stable_argsort", "GarInputError"]
+           "stable_argsort", "GarInputError", "geomed", "cclip", "center_weights", "weighted_sum"]
 
 
 class GarInputError(ValueError):
@@ -423,6 +423,95 @@ def average(gradients, **kwargs):
   n, d, device = _validate(gradients)
   idx = torch.arange(n, dtype=torch.int32, device=device)
   return selected_mean(gradients, idx, n)
+
+
+# ---------------------------------------------------------------------------- #
+# Geometric median and centered clipping: one distance pass, the iteration on scalars, one weighted sum
+
+def check_center_args(mode, param, iters, tol):
+  """The arguments bm_center_weights refuses, refused here with their names (a ValueError)."""
+  name = {"geomed": "nu", "cclip": "tau"}.get(mode)
+  if name is None:
+    raise ValueError(f"unknown mode {mode!r} (geomed, cclip)")
+  if isinstance(param, bool) or not isinstance(param, (int, float)) or not (0 < param < float("inf")):
+    raise ValueError(f"{mode}: {name} must be a positive finite number, got {param!r}")
+  if isinstance(iters, bool) or not isinstance(iters, int) or not 1 <= iters <= _lib.CENTER_MAX_ITERS:
+    raise ValueError(f"{mode}: iters must be an integer within 1..{_lib.CENTER_MAX_ITERS}, got {iters!r}")
+  if isinstance(tol, bool) or not isinstance(tol, (int, float)) or not (0 <= tol < float("inf")):
+    raise ValueError(f"{mode}: tol must be a finite number >= 0, got {tol!r}")
+
+
+def center_weights(sq, n, mode, param, iters, tol=0.0, has_start=False):
+  """The weights of the geometric median ("geomed", param = nu) or of centered clipping ("cclip", param = tau) from the
+  N x N squared distances of the n rows (+ the start vector as point n when has_start), N = n + has_start <= 64 — the
+  iteration of include/bm_gar.h (bm_center_weights) on scalars.  `sq` on the device (where pairwise_sqdist left it,
+  possibly all-reduced): one workgroup, no copy, no synchronisation; `sq` on the host: the host form, same bits.
+  Returns (weights fp64[MAX_ROWS]: the N weights then zeros, info fp64[3]: iterations run, move^2, usable rows), where
+  `sq` lives."""
+  check_center_args(mode, param, iters, tol)
+  N = int(n) + (1 if has_start else 0)
+  if n < 1 or N > _lib.MAX_ROWS:
+    raise GarInputError(f"{mode}: at most {_lib.MAX_ROWS} points (rows + start vector) are supported, got {N}")
+  if sq.dtype != torch.float64 or sq.numel() < N * N or not sq.is_contiguous():
+    raise GarInputError(f"{mode}: expected a contiguous float64 matrix of {N} x {N} squared distances")
+  lib = _lib.load()
+  weights = torch.empty(_lib.MAX_ROWS, dtype=torch.float64, device=sq.device)
+  info = torch.empty(3, dtype=torch.float64, device=sq.device)
+  args = (_ptr(sq), int(n), 1 if has_start else 0, _lib.CENTER_MODES[mode], float(param), int(iters), float(tol),
+          _ptr(weights), _ptr(info))
+  if not sq.is_cuda:
+    _lib.check(lib.bm_center_weights(*args), "bm_center_weights")
+    return weights, info
+  with torch.cuda.device(sq.device):
+    _lib.check(lib.bm_center_weights_device(*args, _stream(sq.device)), "bm_center_weights_device")
+  return weights, info
+
+
+def weighted_sum(gradients, weights):
+  """sum_i float32(weights[i]) * gradients[i], the weights a DEVICE float64 tensor (at least n entries): per coordinate
+  one fused multiply-add per active row, in index order.  Aliased gradients are read once with their weights added;
+  rows of weight 0 are not read; a NaN weight gives NaN everywhere (bm_weighted_sum)."""
+  n, d, device = _validate(gradients)
+  if weights.dtype != torch.float64 or weights.device != device or weights.numel() < n or not weights.is_contiguous():
+    raise GarInputError(f"weights must be a contiguous float64 tensor of at least {n} entries on {device}")
+  lib = _lib.load()
+  out = torch.empty(d, dtype=torch.float32, device=device)
+  if d == 0:
+    return out
+  with torch.cuda.device(device):
+    _lib.check(lib.bm_weighted_sum(_lib.pointer_table(gradients), n, _ptr(weights), d, _ptr(out), _stream(device)),
+               "bm_weighted_sum")
+  return out
+
+
+def _center(mode, gradients, param, iters, tol, start):
+  points = list(gradients) + ([start] if start is not None else [])
+  n = len(gradients)
+  if len(points) > _lib.MAX_ROWS:
+    raise GarInputError(f"{mode}: at most {_lib.MAX_ROWS} gradients are supported"
+                        f"{' (one fewer with a start vector)' if start is not None else ''}, got {n}")
+  check_center_args(mode, param, iters, tol)
+  _validate(points)
+  weights, _ = center_weights(pairwise_sqdist(points), n, mode, param, iters, tol, start is not None)
+  return weighted_sum(points, weights)
+
+
+def geomed(gradients, f=None, nu=1e-6, iters=8, tol=0.0, **kwargs):
+  """The geometric median by `iters` smoothed Weiszfeld iterations (RFA) from the mean of the rows:
+  v <- sum_i w_i x_i / sum_i w_i, w_i = 1 / max(nu, |x_i - v|).  One distance pass over the n rows, the iteration on the
+  n weights (bm_center_weights_device), one weighted sum — whatever `iters` is; no host synchronisation.  `f` is
+  accepted and ignored (the registry's calling convention).  n <= 64."""
+  return _center("geomed", gradients, nu, iters, tol, None)
+
+
+def cclip(gradients, f=None, tau=None, iters=3, tol=0.0, start=None, **kwargs):
+  """Centered clipping: v <- v + (1/n) sum_i (x_i - v) min(1, tau / |x_i - v|), `iters` times from `start` (a vector like
+  the gradients, e.g. the previous aggregate; None: the mean of the rows).  One distance pass over the rows and the
+  start, the iteration on scalars, one weighted sum.  `tau` is required; `f` is accepted and ignored.  n <= 64 without a
+  start, 63 with one."""
+  if tau is None:
+    raise ValueError("cclip: tau (the clipping radius) is required")
+  return _center("cclip", gradients, tau, iters, tol, start)
 
 
 def cge_selection(gradients, f, **kwargs):

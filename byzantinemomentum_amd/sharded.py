@@ -113,7 +113,7 @@ class HipBackend:
   capabilities = frozenset((
     "step_worker", "momentum_stats_colwise", "momentum_stats_sqdist", "stack_stats_colwise", "stack_stats_sqdist",
     "device_search", "attack_ranking_device", "bulyan_pass2_eval", "order_pair", "colwise_eval", "sqdist2", "anticge",
-    "accept_count", "attack_vector"))
+    "accept_count", "attack_vector", "center_weights", "weighted_sum"))
 
   def __init__(self):
     from . import gars, stats
@@ -150,6 +150,14 @@ class HipBackend:
   def brute_select_device(self, sq, n, f):
     """(sel, status) on the device; status -1 = no subset of n - f rows has a finite diameter (brute.py:68)."""
     return self.gars.brute_select_device(sq, n, f)
+
+  def center_weights(self, sq, n, mode, param, iters, tol, has_start):
+    """The weights of the geometric median / centered clipping from the (all-reduced) squared distances, where they
+    are (bm_center_weights_device: one workgroup, no synchronisation): (weights fp64[MAX_ROWS], info fp64[3])."""
+    return self.gars.center_weights(sq, n, mode, param, iters, tol, has_start)
+
+  def weighted_sum(self, gradients, weights):
+    return self.gars.weighted_sum(gradients, weights)
 
   def sharded_rule(self, name, comm, gradients, f, m, d_total=None, with_order=False):
     """Multi-Krum / Bulyan of the local slice in one C call (bm_sharded_krum / bm_sharded_bulyan);
@@ -311,6 +319,72 @@ def _attack_vector_torch(kind, avg, factor, target, want_direction):
   return (out, direction) if want_direction else out
 
 
+def _center_weights_torch(sq, n, mode, param, iters, tol, has_start):
+  """bm_center_weights in plain torch (fp64, where `sq` lives) for a backend without the kernel: the iteration of
+  include/bm_gar.h on the weights — (weights fp64[MAX_ROWS], info fp64[3])."""
+  N = n + (1 if has_start else 0)
+  D = sq[:N, :N].to(torch.float64)
+  weights = torch.zeros(_lib.MAX_ROWS, dtype=torch.float64, device=sq.device)
+  off = ~torch.eye(N, dtype=torch.bool, device=sq.device)
+  bad = (~torch.isfinite(D) & off).sum(dim=1)
+  usable = ~((bad > 0) & (2 * bad >= N - 1))
+  rows = usable.clone()
+  rows[n:] = False
+  U = int(rows.sum())
+  if U == 0:
+    weights[:N] = math.nan
+    return weights, torch.tensor([0.0, math.nan, 0.0], dtype=torch.float64, device=sq.device)
+  Dz = torch.where(torch.isfinite(D), D, torch.zeros_like(D))  # (a term of weight 0 is skipped, whatever D holds)
+  blind = ~torch.isfinite(D)
+  c = torch.zeros(N, dtype=torch.float64, device=sq.device)
+  if has_start and bool(usable[n]):
+    c[n] = 1.0
+  else:
+    c[rows] = 1.0 / U
+
+  def dot_rows(w):  # sum_j w_j D_ij with the terms of weight 0 skipped; NaN where a term that counts is not finite
+    t = Dz @ w
+    return torch.where((blind & (w != 0)[None, :]).any(dim=1), torch.full_like(t, math.nan), t)
+
+  done, move2 = 0, 0.0
+  for _ in range(iters):
+    t = dot_rows(c)
+    q = (c * torch.where(c != 0, t, torch.zeros_like(t))).sum()
+    r2 = t - 0.5 * q
+    r = torch.where(torch.isfinite(r2), r2.clamp_min(0.0).sqrt(), torch.full_like(r2, math.inf))
+    if mode == "geomed":
+      w = torch.where(rows, 1.0 / r.clamp_min(param), torch.zeros_like(r))
+      nxt = w / w.sum()
+    else:
+      s = torch.where(rows, torch.where(r <= param, torch.ones_like(r), param / r), torch.zeros_like(r))
+      nxt = c * (1.0 - s.sum() / U) + s / U
+    e = nxt - c
+    c = nxt
+    u = dot_rows(e)
+    move2 = max(0.0, -0.5 * float((e * torch.where(e != 0, u, torch.zeros_like(u))).sum()))
+    done += 1
+    if tol > 0 and math.sqrt(move2) <= tol:
+      break
+  weights[:N] = c
+  return weights, torch.tensor([float(done), move2, float(U)], dtype=torch.float64, device=sq.device)
+
+
+def _weighted_sum_torch(points, weights):
+  """bm_weighted_sum in plain torch, accumulated in fp64: rows that are one tensor once, with their weights added; rows
+  of weight 0 are not read; a NaN weight gives NaN everywhere."""
+  w = weights[:len(points)].tolist()
+  if any(math.isnan(x) for x in w):
+    return torch.full_like(points[0], math.nan)
+  groups = {}
+  for p, x in zip(points, w):
+    groups.setdefault(id(p), [p, 0.0])[1] += x
+  acc = torch.zeros(points[0].shape, dtype=torch.float64, device=points[0].device)
+  for p, x in groups.values():
+    if x != 0.0:
+      acc.add_(p.double(), alpha=x)
+  return acc.to(points[0].dtype)
+
+
 class ShardedAggregator:
   """Aggregation rules over gradients whose coordinates are sharded across the ranks of `group`."""
 
@@ -343,7 +417,11 @@ class ShardedAggregator:
     # HIP backend; after a single-call krum a view of the stream's workspace: read it on that stream before the next
     # sharded rule).  step.AggregationStep counts the Byzantine rows among them (attack.py:822)
     self.last_selection = None
-    self._total = None        # (length of the whole vectors, this rank's shard length when it was determined)
+    # the weights of the latest geomed / cclip of THIS aggregator (fp64[MAX_ROWS] where the rule left them) and its
+    # info (iterations run, move^2, usable rows)
+    self.last_weights = None
+    self.last_center_info = None
+    self._total = None       # (length of the whole vectors, this rank's shard length when it was determined)
 
   def shard_rows(self, rows, d=None):
     """This rank's slice (shard_bounds) of n whole gradients held on every rank, as `Shards` carrying the total."""
@@ -604,6 +682,40 @@ class ShardedAggregator:
     order = self.backend.argsort(sq, n)
     self.last_selection = (order, n - f)
     return self.backend.selected_mean(local, order, n - f)
+
+  def _center(self, mode, local, param, iters, tol, start, d_total):
+    """The geometric median / centered clipping of the local slice: (1) the squared distances of rows + [start],
+    all-reduced — the one collective, N x N doubles; (2) the weights of the iterate, every rank from the same matrix:
+    the same bits; (3) the weighted sum of the local slice.  No host synchronisation and no d-sized collective,
+    whatever `iters` is.  A backend that declares the "center_weights" / "weighted_sum" capabilities runs (2) / (3) as
+    kernels; any other gets the same steps in plain torch, in fp64."""
+    from . import gars
+    gars.check_center_args(mode, param, iters, tol)
+    rows = list(local)
+    points = rows + ([start] if start is not None else [])
+    if not rows or len(points) > _lib.MAX_ROWS:
+      raise gars.GarInputError(f"{mode}: 1..{_lib.MAX_ROWS} gradients are supported"
+                               f"{' (one fewer with a start vector)' if start is not None else ''}, got {len(rows)}")
+    caps = getattr(self.backend, "capabilities", ())
+    sq = self.global_sqdist(points, self._total_of(local, d_total))
+    args = (sq, len(rows), mode, param, iters, tol, start is not None)
+    weights, info = self.backend.center_weights(*args) if "center_weights" in caps else _center_weights_torch(*args)
+    self.last_weights, self.last_center_info = weights, info
+    if "weighted_sum" in caps:
+      return self.backend.weighted_sum(points, weights)
+    return _weighted_sum_torch(points, weights)
+
+  def geomed(self, local, f=None, nu=1e-6, iters=8, tol=0.0, d_total=None):
+    """The geometric median by `iters` smoothed Weiszfeld iterations from the mean of the rows (gars.geomed).
+    `self.last_weights` keeps the weights (device fp64[MAX_ROWS]: the n weights, then zeros).  f is ignored."""
+    return self._center("geomed", local, nu, iters, tol, None, d_total)
+
+  def cclip(self, local, f=None, tau=None, iters=3, tol=0.0, start=None, d_total=None):
+    """Centered clipping from `start` (this rank's slice of it; None: the mean of the rows), gars.cclip.
+    `self.last_weights` keeps the weights, the start's being entry n.  tau is required; f is ignored."""
+    if tau is None:
+      raise ValueError("cclip: tau (the clipping radius) is required")
+    return self._center("cclip", local, tau, iters, tol, start, d_total)
 
   def anticge(self, local_honests, f_decl, f_real):
     """The reference's `anticge` attack (attacks/anticge.py:49-78) on this rank's slice of the honest gradients:

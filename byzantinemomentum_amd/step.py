@@ -54,7 +54,8 @@ from . import _lib, linesearch
 
 __all__ = ["AggregationStep"]
 
-_RULES = ("krum", "bulyan", "median", "trmean", "phocas", "meamed", "aksel", "brute", "average", "cge")
+_RULES = ("krum", "bulyan", "median", "trmean", "phocas", "meamed", "aksel", "brute", "average", "cge", "geomed", "cclip")
+_CENTER = {"geomed": ("nu", "iters", "tol"), "cclip": ("tau", "iters", "tol")}  # rule -> the `gar_args` it takes
 _COLWISE = ("median", "trmean", "phocas", "meamed")
 _DISTANCE = ("krum", "bulyan")
 MAX_PAST = 4096  # past sampled averages kept for the curvature term (each is one d-vector of device memory)
@@ -161,6 +162,10 @@ class AggregationStep:
     single_call: with the HIP backend, worker-side momentum and a rule the C entry point knows
     (krum, bulyan, median, trmean, phocas, meamed), run() is ONE call into libbm_gar.so (bm_step_worker),
     collectives included; False keeps the kernel-by-kernel Python sequence (same kernels, same results).
+    gar: a rule of the reference, or "geomed" (gar_args nu / iters / tol) / "cclip" (gar_args tau — required — / iters /
+    tol): one distance pass, the iteration on scalars, one weighted sum (ShardedAggregator.geomed / .cclip); plain first
+    pass, the generic factor search, no acceptation ratio, never the single call.  Centered clipping starts from the
+    previous step's defense vector (`cclip_start`; the mean of the rows on the first step).
     attack: "empire" / "little" (attacks/identical.py), or "anticge" (attacks/anticge.py: no factor — `attack_factor` is
     ignored, `attack_evals` must be None, and 1 <= nb_decl_byz <= honest workers); it runs as its own short chain behind
     the plain first pass (ShardedAggregator.anticge), with every momentum placement, clipping and rule.
@@ -182,6 +187,15 @@ class AggregationStep:
     the device once per evaluation like the reference does, the cursor on the host."""
     if gar not in _RULES:
       raise ValueError(f"unknown aggregation rule {gar!r}")
+    if gar in _CENTER:
+      # geomed: nu / iters / tol; cclip: tau (required) / iters / tol — checked here, not at the first step
+      from . import gars
+      args, (radius, _, _) = dict(gar_args or {}), _CENTER[gar]
+      if set(args) - set(_CENTER[gar]):
+        raise ValueError(f"gar_args of {gar} holds {_CENTER[gar]} and nothing else, got {sorted(args)}")
+      if gar == "cclip" and "tau" not in args:
+        raise ValueError("cclip: gar_args must hold tau (the clipping radius)")
+      gars.check_center_args(gar, args.get(radius, 1e-6), args.get("iters", 1), args.get("tol", 0.0))
     if momentum_at not in ("worker", "server", "update"):
       raise ValueError(f"momentum_at must be 'worker', 'server' or 'update', got {momentum_at!r}")
     if attack not in _ATTACKS:
@@ -249,6 +263,9 @@ class AggregationStep:
     self._pending = None
     self._update = None
     self._prev_stats = None    # single-call form: the previous step's reduced statistics (slot 0 = ||avg_s||^2)
+    # cclip: the vector the clipping starts from, the previous step's defense vector (None before the first step: the
+    # mean of the rows).  Advanced by _defense alone — the evaluations of a factor search read it and leave it
+    self.cclip_start = None
     self.plan = self._make_plan(single_call)
     self.single_call = self.plan.single_call
 
@@ -346,6 +363,8 @@ class AggregationStep:
       # alone): no admissible subset raises like brute.py:68, a device search that ran out of its node budget is
       # repeated on the host
       return agg.brute(gradients, f, check=True, **self.gar_args)
+    if self.gar == "cclip":
+      return agg.cclip(gradients, f, start=self.cclip_start, **self.gar_args)
     return getattr(agg, self.gar)(gradients, f, **self.gar_args)
 
   def _fetch(self, matrix):
@@ -649,7 +668,10 @@ class AggregationStep:
       return first.fused_defense
     if first.fused_sq is not None:
       return self.agg.rule_from_sq(self.gar, first.honests + attacks, first.fused_sq, self.f_decl, self.gar_args.get("m"))
-    return self._aggregate(first.honests + attacks)
+    defense = self._aggregate(first.honests + attacks)
+    if self.gar == "cclip":
+      self.cclip_start = defense  # the next step clips around this one's aggregate (never written again: no clone)
+    return defense
 
   def _update_momentum(self, defense):
     """Step 4 (attack.py:832-839): what update_gradient() hands out."""

@@ -544,6 +544,46 @@ int bm_search_device_next(void* state, const double* y, int negative, int last, 
  * bm_bulyan_pass2 with this ranking instead of a distance pass over the n rows as well.  m <= 0: n - f - 2. */
 int bm_attack_ranking(const double* ext, int h, int k, int f, int mode, int m, double t, int32_t* order_out);
 
+/* ---------------------------------------------------------------------------------------------
+ * The geometric median (RFA, smoothed Weiszfeld) and centered clipping from ONE distance pass.  These three entry
+ * points joined ABI 23: additions only, no signature changed.  Neither rule exists in the reference.
+ *
+ * Every iterate of both rules is an affine combination v = sum_j c_j p_j (sum c = 1) of the points p_0 .. p_{N-1}: the
+ * n rows and, when has_start != 0, a start vector as point n (N = n + has_start <= BM_MAX_ROWS).  With D the N x N
+ * squared distances of the points (bm_pairwise_sqdist over rows + [start]),
+ *     |p_i - v|^2 = t_i - q / 2,   t_i = sum_j c_j D_ij,   q = sum_i c_i t_i,
+ * so the whole iteration runs on the N weights (csrc/center_core.h, one definition for host and device) and the rule
+ * costs one distance pass plus one bm_weighted_sum whatever the number of iterations.
+ *   usable    point i is unusable when D_ij is non-finite for at least one and at least half of the other points
+ *             (cnt >= 1 and 2 cnt >= N - 1): it never gets weight.  No usable ROW: every weight is NaN.  U = the
+ *             number of usable rows.
+ *   start     c = 1 on the start vector when it is given and usable, else 1 / U on every usable row.
+ *   distance  r_i = sqrt(max(0, t_i - q / 2)); terms with c_j == 0 are skipped; a non-finite r_i^2 counts as +inf
+ *             (aggregators/krum.py:46-47).
+ *   BM_CENTER_GEOMED (param = nu > 0): w_i = 1 / max(nu, r_i) over the usable rows, c <- w / sum w (the start gets 0).
+ *   BM_CENTER_CCLIP  (param = tau > 0): s_i = 1 if r_i <= tau else tau / r_i over the usable rows, S = sum s_i,
+ *             c <- c * (1 - S / U), then c_i += s_i / U on the rows: v <- v + (1/U) sum_i (x_i - v) min(1, tau / |x_i - v|).
+ *   stop      after `iters` iterations (1 .. 64), or earlier once sqrt(move^2) <= tol, move^2 = max(0, -1/2 sum_jk e_j e_k
+ *             D_jk) being the squared length of the step (e = the change of c); tol = 0 never stops early.
+ * weights_out: BM_MAX_ROWS doubles, the N weights, then zeros.  info_out: 3 doubles = { iterations run, move^2 of the
+ * last one, U }.
+ * bm_center_weights: HOST function on a HOST matrix, no stream.  bm_center_weights_device: the same on the DEVICE matrix
+ * where bm_pairwise_sqdist left it, one workgroup, no copy, no synchronisation; the same bits as the host form.  Both
+ * return BM_EINVAL for a bad n, has_start, mode, param, iters or tol before any HIP call. */
+enum bm_center_mode { BM_CENTER_GEOMED = 0, BM_CENTER_CCLIP = 1 };
+int bm_center_weights(const double* sq_host, int n, int has_start, int mode, double param, int iters, double tol,
+                      double* weights_out, double* info_out);
+int bm_center_weights_device(const double* sq_dev, int n, int has_start, int mode, double param, int iters, double tol,
+                             double* weights_out_dev, double* info_out_dev, void* stream);
+
+/* out[j] = sum_i w_i rows[i][j] with w_i = (float)weights[i] (weights: DEVICE, n doubles, e.g. where
+ * bm_center_weights_device left them): acc = 0, then acc = fmaf(w_i, rows[i][j], acc) over the ACTIVE rows in index order.
+ * Rows that are the same pointer form one group: their fp64 weights are added in index order, rounded to fp32 once, and
+ * the row is read once, at its first index.  A group whose fp32 weight is exactly 0 is not read (an excluded NaN row
+ * cannot poison the sum).  A NaN weight makes out NaN everywhere.  One pass, no workspace, no synchronisation; d == 0
+ * launches nothing. */
+int bm_weighted_sum(const float* const* rows, int n, const double* weights_dev, int64_t d, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

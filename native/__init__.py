@@ -150,6 +150,28 @@ def _register_extra():
   register("native-cge", _gars.cge, _reference_check("cge", _check_list), influence=_influence_cge)
 
 
+_center_registered = False
+
+
+def register_center_rules():
+  """Register `native-geomed` and `native-cclip` with the reference's registry: the two rules the reference does not
+  ship (the geometric median and centered clipping, byzantinemomentum_amd.gars).  NOT done at import — the names
+  `import aggregators` registers by itself stay the reference's own rule set — so a driver that wants them calls this
+  once after `import aggregators` (`--gar native-geomed`, `--gar native-cclip --gar-args tau:...`).  No `check` of the
+  reference to borrow and no selection an `influence` could count; cclip is stateless here (the registry has nowhere
+  to keep a start vector: every call starts from the mean of the rows).  Returns the names registered."""
+  global _center_registered
+  agg = sys.modules.get("aggregators")
+  register = getattr(agg, "register", None)
+  if register is None or not hasattr(agg, "gars"):
+    raise RuntimeError("native.register_center_rules() needs the reference's `aggregators` package imported first")
+  if not _center_registered:
+    _center_registered = True
+    register("native-geomed", _gars.geomed, _generic_check())
+    register("native-cclip", _gars.cclip, _generic_check())
+  return ["native-geomed", "native-cclip"]
+
+
 _bound = False
 
 
