@@ -8,12 +8,12 @@
 // writes their sum S in the reference's order of additions and leaves |S|^2 (fp64, fixed reduction tree, no float
 // atomics); bm_anticge_scale: S *= -nextafter(norm_(maxpos), 0) / |S| from the two scalars where they are.  Nothing
 // synchronises with the host; under sharding the caller all-reduces ONE double between the two calls.
-#include "bm_common.h"
 #include "rank_body.h"
+#include "table_sum.h"
 
 namespace bm {
 
-constexpr int kAcgBlock = 256;
+constexpr int kAcgScaleBlock = 256;  // lanes per workgroup of the scaling kernel (the sum: kTableBlock, table_sum.h)
 constexpr int kAcgMaxBlocks = 256 * 32;  // workgroups of the plain form per piece of the pass
 constexpr Caps kAcgCaps = caps_of(kAcgMaxBlocks);  // one fp64 partial per workgroup: at most kAcgCaps.sets() per piece
 constexpr int kAcgScaleBlocks = 2048;
@@ -39,46 +39,17 @@ __global__ __launch_bounds__(64) void anticge_rank_kernel(const double* __restri
 // followed by one `attack.add_(g)` per selected row, g_(0) first (anticge.py:70-72; with maxpos = 0 the clone alone).
 // One fp64 partial of sum_j S_j^2 per workgroup: every product exact in fp64, lanes and waves through the fixed tree.
 template <int VEC>
-__global__ __launch_bounds__(kAcgBlock) void anticge_sum_kernel(RowTable rows, const int32_t* __restrict__ order,
+__global__ __launch_bounds__(kTableBlock) void anticge_sum_kernel(RowTable rows, const int32_t* __restrict__ order,
                                                                 int maxpos, int64_t nvec, float* __restrict__ out,
                                                                 int tail, double* __restrict__ partial) {
   __shared__ const float* sel[BM_MAX_ROWS];
-  __shared__ double red[kAcgBlock / 64];
+  __shared__ double red[kTableBlock / 64];
   const int m = maxpos > 0 ? maxpos : 1;  // rows read
   if ((int)threadIdx.x < m) sel[threadIdx.x] = rows.p[load_index_coherent(order + threadIdx.x) & (BM_MAX_ROWS - 1)];
   __syncthreads();
   double wide = 0.0;
-  const int64_t nblk = (nvec + kAcgBlock - 1) / kAcgBlock;
-  for (int64_t b = blockIdx.x; b < nblk; b += gridDim.x) {
-    const int64_t v = b * kAcgBlock + threadIdx.x;
-    if (v >= nvec) continue;
-    float acc[VEC];
-    load_stream<VEC>(sel[0] + v * VEC, acc);
-    if (maxpos > 0) {
-#pragma unroll
-      for (int c = 0; c < VEC; ++c) acc[c] += acc[c];
-    }
-#pragma unroll 8
-    for (int k = 1; k < m; ++k) {
-      float t[VEC];
-      load_stream<VEC>(sel[k] + v * VEC, t);
-#pragma unroll
-      for (int c = 0; c < VEC; ++c) acc[c] += t[c];
-    }
-    store_stream<VEC>(out + v * VEC, acc);
-#pragma unroll
-    for (int c = 0; c < VEC; ++c) wide += (double)acc[c] * (double)acc[c];
-  }
-  // the d % VEC trailing columns: one lane each, in the last workgroup (no second launch)
-  if (blockIdx.x == gridDim.x - 1 && (int)threadIdx.x < tail) {
-    const int64_t j = nvec * VEC + threadIdx.x;
-    float acc = sel[0][j];
-    if (maxpos > 0) acc += acc;
-    for (int k = 1; k < m; ++k) acc += sel[k][j];
-    out[j] = acc;
-    wide += (double)acc * (double)acc;
-  }
-  const double r = block_reduce_sum<kAcgBlock>(wide, red);
+  table_sum_plain<VEC>(sel, m, nvec, tail, out, AnticgeFold{maxpos > 0}, [&](float x) { wide += (double)x * (double)x; });
+  const double r = block_reduce_sum<kTableBlock>(wide, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = r;
 }
 
@@ -106,13 +77,13 @@ __device__ __forceinline__ bool anticge_multiplier(const double* __restrict__ sc
 }
 
 template <int VEC>
-__global__ __launch_bounds__(kAcgBlock) void anticge_scale_kernel(float* __restrict__ vec, int64_t nvec,
+__global__ __launch_bounds__(kAcgScaleBlock) void anticge_scale_kernel(float* __restrict__ vec, int64_t nvec,
                                                                   const double* __restrict__ scal) {
   float mult;
   if (!anticge_multiplier(scal, &mult)) return;
   using T = typename VecLoad<VEC>::T;
-  const int64_t stride = (int64_t)gridDim.x * kAcgBlock;
-  for (int64_t v = (int64_t)blockIdx.x * kAcgBlock + threadIdx.x; v < nvec; v += stride) {
+  const int64_t stride = (int64_t)gridDim.x * kAcgScaleBlock;
+  for (int64_t v = (int64_t)blockIdx.x * kAcgScaleBlock + threadIdx.x; v < nvec; v += stride) {
     T x = *reinterpret_cast<const T*>(vec + v * VEC);
     if constexpr (VEC == 1) {
       x = x * mult;
@@ -156,8 +127,8 @@ extern "C" int bm_anticge_sum(const float* const* rows, int h, int64_t d, int f_
   int nparts = 0;
   // (the d % VEC trailing columns ride in the last workgroup of a piece's launch: no launch, no partial of their own)
   const int rc = for_pieces(d, [&](int64_t lo, int64_t dp) {
-    return for_body_and_tail<4>(Tail::kRidesNarrowed, vec, dp, kAcgBlock, kAcgCaps, [&](auto width, const Span& sp) {
-      hipLaunchKernelGGL(anticge_sum_kernel<decltype(width)::value>, dim3(sp.grid), dim3(kAcgBlock), 0, s,
+    return for_body_and_tail<4>(Tail::kRidesNarrowed, vec, dp, kTableBlock, kAcgCaps, [&](auto width, const Span& sp) {
+      hipLaunchKernelGGL(anticge_sum_kernel<decltype(width)::value>, dim3(sp.grid), dim3(kTableBlock), 0, s,
                          tab.advanced(lo), order, maxpos, sp.count, sum_out + lo, sp.tail, partial + sp.part);
       BM_LAUNCH_CHECK();
       return 0;
@@ -175,9 +146,9 @@ extern "C" int bm_anticge_scale(float* vec, int64_t d, const double* scal, void*
   if (scal == nullptr || d < 0 || (d > 0 && vec == nullptr)) return BM_EINVAL;
   if (d == 0) return 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  return for_body_and_tail<4>(Tail::kOwnLaunch, Alignment().of(vec).vec(), d, kAcgBlock, caps_of(kAcgScaleBlocks),
+  return for_body_and_tail<4>(Tail::kOwnLaunch, Alignment().of(vec).vec(), d, kAcgScaleBlock, caps_of(kAcgScaleBlocks),
                               [&](auto width, const Span& sp) {
-    hipLaunchKernelGGL(anticge_scale_kernel<decltype(width)::value>, dim3(sp.grid), dim3(kAcgBlock), 0, s,
+    hipLaunchKernelGGL(anticge_scale_kernel<decltype(width)::value>, dim3(sp.grid), dim3(kAcgScaleBlock), 0, s,
                        vec + sp.first, sp.count, scal);
     BM_LAUNCH_CHECK();
     return 0;

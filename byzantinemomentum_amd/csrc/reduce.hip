@@ -10,6 +10,7 @@
 // across lanes/workgroups, no float atomics) and no host synchronisation.
 #include "bm_common.h"
 #include "rank_body.h"
+#include "table_sum.h"
 
 namespace bm {
 
@@ -19,113 +20,44 @@ constexpr Caps kStatsCaps{kMaxPartialBlocks - 1, kMaxPartialBlocks};  // bm_stac
 constexpr int kMeanMaxBlocks = 256 * 32;
 
 // ---------------------------------------------------------------------------
-// selected_mean: out = (((0 + R[idx0]) + R[idx1]) + ... ) / m, sequential fp32.
+// selected_mean: out = (((0 + R[idx0]) + R[idx1]) + ... ) / m, sequential fp32 (MeanFold, table_sum.h).
 // ---------------------------------------------------------------------------
-template <int VEC>
-__global__ __launch_bounds__(kRedBlock) void selected_mean_kernel(RowTable rows,
-                                                                  const int32_t* __restrict__ idx,
-                                                                  int m, int64_t nvec, float fm, int nt_result,
-                                                                  float* __restrict__ out, int tail) {
-  __shared__ const float* sel[BM_MAX_ROWS];
+static_assert(kRedBlock == kTableBlock, "bm_selected_mean cuts its pass for kRedBlock lanes; the plain driver walks kTableBlock");
+
+// sel[k] = the row idx[k] names; returns the divisor.  A NEGATIVE index is the Brute search saying "no selection, do not
+// use this" (brute.hip): the divisor is then NaN, the mean NaN everywhere.  Every lane of the workgroup must call.
+__device__ __forceinline__ float selected_mean_prologue(const RowTable& rows, const int32_t* __restrict__ idx, int m,
+                                                        float fm, const float** sel) {
   __shared__ int poisoned;
   if (threadIdx.x == 0) poisoned = 0;
   __syncthreads();
   if (threadIdx.x < m) {
-    // (a NEGATIVE index is the Brute search saying "no selection, do not use this", brute.hip: the mean is then NaN
-    //  everywhere instead of the average of some rows)
     const int i = load_index_coherent(idx + threadIdx.x);
     if (i < 0) poisoned = 1;
     sel[threadIdx.x] = rows.p[i < 0 ? 0 : i];
   }
   __syncthreads();
-  if (poisoned) fm = __builtin_nanf("");
-  const int64_t nblk = (nvec + kRedBlock - 1) / kRedBlock;
-  for (int64_t b = blockIdx.x; b < nblk; b += gridDim.x) {
-    const int64_t v = b * kRedBlock + threadIdx.x;
-    if (v >= nvec) continue;
-    float acc[VEC];
-#pragma unroll
-    for (int c = 0; c < VEC; ++c) acc[c] = 0.0f;
-#pragma unroll 8
-    for (int k = 0; k < m; ++k) {
-      float t[VEC];
-      load_stream<VEC>(sel[k] + v * VEC, t);
-#pragma unroll
-      for (int c = 0; c < VEC; ++c) acc[c] += t[c];
-    }
-#pragma unroll
-    for (int c = 0; c < VEC; ++c) acc[c] = acc[c] / fm;
-    store_result_policy<VEC>(out + v * VEC, acc, nt_result);
-  }
-  // the d % VEC trailing columns: one lane each, in the last workgroup (no second launch)
-  if (VEC > 1 && blockIdx.x == gridDim.x - 1 && (int)threadIdx.x < tail) {
-    const int64_t j = nvec * VEC + threadIdx.x;
-    float acc = 0.0f;
-    for (int k = 0; k < m; ++k) acc += sel[k][j];
-    out[j] = acc / fm;
-  }
+  return poisoned ? __builtin_nanf("") : fm;
 }
 
-// Burst form of the same kernel for long gradients (16-byte columns): one workgroup of 1024 lanes per CU,
-// column groups interleaved across the CUs, the results of 9 iterations staged in LDS, a barrier, then written
-// back to back — the recipe of colwise_burst_kernel (colwise_kernels.h), where the why is written down.  The
-// additions per column are the same, in the same order: the result is bit-identical to the plain form.
-constexpr int kMeanBurstThreads = 1024;
-constexpr int kMeanBurstSlots = 9;  // 9 x 1024 x 16 B = 144 KB of results next to the pointer table
-__global__ __launch_bounds__(kMeanBurstThreads) void selected_mean_burst_kernel(RowTable rows,
-                                                                                const int32_t* __restrict__ idx, int m,
-                                                                                int64_t nvec, float fm,
-                                                                                float* __restrict__ out, int tail) {
-  using V = typename VecLoad<4>::T;
-  __shared__ V stage[kMeanBurstSlots * kMeanBurstThreads];
+template <int VEC>
+__global__ __launch_bounds__(kTableBlock) void selected_mean_kernel(RowTable rows, const int32_t* __restrict__ idx, int m,
+                                                                    int64_t nvec, float fm, float* __restrict__ out, int tail) {
   __shared__ const float* sel[BM_MAX_ROWS];
-  __shared__ int poisoned;
-  const uint32_t tid = threadIdx.x;
-  if (tid == 0) poisoned = 0;
-  __syncthreads();
-  if ((int)tid < m) {
-    const int i = load_index_coherent(idx + tid);  // (negative: no selection — the mean is NaN, see selected_mean_kernel)
-    if (i < 0) poisoned = 1;
-    sel[tid] = rows.p[i < 0 ? 0 : i];
-  }
-  __syncthreads();
-  if (poisoned) fm = __builtin_nanf("");
-  const uint32_t nv = (uint32_t)nvec;
-  const uint32_t span = gridDim.x * kMeanBurstThreads;
-  const uint32_t iters = (nv + span - 1) / span;
-  const uint32_t first = blockIdx.x * kMeanBurstThreads + tid;
-  for (uint32_t p0 = 0; p0 < iters; p0 += kMeanBurstSlots) {
-    const uint32_t p1 = (p0 + kMeanBurstSlots < iters) ? p0 + kMeanBurstSlots : iters;
-    for (uint32_t it = p0; it < p1; ++it) {
-      const uint32_t v = it * span + first;
-      if (v < nv) {
-        float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll 8
-        for (int k = 0; k < m; ++k) {
-          float t[4];
-          load_stream<4>(sel[k] + (int64_t)v * 4, t);
-#pragma unroll
-          for (int c = 0; c < 4; ++c) acc[c] += t[c];
-        }
-        V packed;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) packed[c] = acc[c] / fm;
-        stage[(it - p0) * kMeanBurstThreads + tid] = packed;
-      }
-    }
-    __syncthreads();  // what makes the stores below a burst
-    for (uint32_t it = p0; it < p1; ++it) {
-      const uint32_t v = it * span + first;
-      if (v < nv) __builtin_nontemporal_store(stage[(it - p0) * kMeanBurstThreads + tid], reinterpret_cast<V*>(out) + v);
-    }
-  }
-  // the d % 4 trailing columns: one lane each, in the last workgroup (no second launch: 4.4 us of a C3 aggregation)
-  if (blockIdx.x == gridDim.x - 1 && (int)tid < tail) {
-    const int64_t j = nvec * 4 + tid;
-    float acc = 0.0f;
-    for (int k = 0; k < m; ++k) acc += sel[k][j];
-    out[j] = acc / fm;
-  }
+  const MeanFold fold{selected_mean_prologue(rows, idx, m, fm, sel)};
+  table_sum_plain<VEC>(sel, m, nvec, tail, out, fold);
+}
+
+// Burst form of the same kernel for long gradients (table_sum_burst): 9 x 1024 x 16 B = 144 KB of results next to the
+// pointer table.
+constexpr int kMeanBurstThreads = 1024;
+constexpr int kMeanBurstSlots = 9;
+__global__ __launch_bounds__(kMeanBurstThreads) void selected_mean_burst_kernel(RowTable rows, const int32_t* __restrict__ idx,
+                                                                                int m, int64_t nvec, float fm,
+                                                                                float* __restrict__ out, int tail) {
+  __shared__ const float* sel[BM_MAX_ROWS];
+  const MeanFold fold{selected_mean_prologue(rows, idx, m, fm, sel)};
+  table_sum_burst<kMeanBurstThreads, kMeanBurstSlots>(sel, m, nvec, tail, out, fold);
 }
 
 template <int VEC>
@@ -144,8 +76,8 @@ static int launch_selected_mean(const RowTable& tab, const int32_t* idx, int m, 
       return 0;
     }
   }
-  hipLaunchKernelGGL(selected_mean_kernel<VEC>, dim3(sp.grid), dim3(kRedBlock), 0, s, tab, idx, m, nvec,
-                     (float)m, 1, out, sp.tail);
+  hipLaunchKernelGGL(selected_mean_kernel<VEC>, dim3(sp.grid), dim3(kTableBlock), 0, s, tab, idx, m, nvec,
+                     (float)m, out, sp.tail);
   BM_LAUNCH_CHECK();
   return 0;
 }

@@ -1,11 +1,11 @@
 // weighted_sum.hip — out = sum_i w_i rows[i], the weights read from DEVICE memory: the last leg of the geometric median
 // and of centered clipping (bm_center_weights_device leaves the weights where this kernel reads them).  ONE streaming
-// pass over the rows that carry weight; per coordinate acc = 0, then acc = fmaf(w_i, x_i, acc) in index order.
-#include "bm_common.h"
+// pass over the rows that carry weight; per coordinate acc = 0, then acc = fmaf(w_i, x_i, acc) in index order
+// (WeightedFold under the plain driver of table_sum.h; no burst form yet).
+#include "table_sum.h"
 
 namespace bm {
 
-constexpr int kWsumBlock = 256;
 constexpr int kWsumMaxBlocks = 256 * 32;
 
 // first[i] = the lowest index whose pointer is rows[i]: rows that are one pointer (the f copies of a Byzantine vector,
@@ -14,10 +14,10 @@ struct RowGroups {
   uint8_t first[BM_MAX_ROWS];
 };
 
-// The active rows of a launch, decided once per workgroup (as selected_mean_kernel builds its sel[]): the weight of a
-// group is the sum of its members' fp64 weights in index order, rounded to fp32; a group whose fp32 weight is exactly
-// 0 is dropped (never read: an excluded NaN row cannot poison the sum); a NaN weight poisons the launch.  Returns the
-// number of active groups, -1 when poisoned.  Every lane of the workgroup must call.
+// The active rows of a launch, decided once per workgroup (as selected_mean_prologue, reduce.hip, builds its sel[]):
+// the weight of a group is the sum of its members' fp64 weights in index order, rounded to fp32; a group whose fp32
+// weight is exactly 0 is dropped (never read: an excluded NaN row cannot poison the sum); a NaN weight poisons the
+// launch.  Returns the number of active groups, -1 when poisoned.  Every lane of the workgroup must call.
 __device__ __forceinline__ int weighted_sum_prologue(const RowTable& rows, const RowGroups& groups,
                                                      const double* __restrict__ weights, int n, const float** sel,
                                                      float* wt, double* wd, int* count) {
@@ -48,10 +48,9 @@ __device__ __forceinline__ int weighted_sum_prologue(const RowTable& rows, const
 }
 
 template <int VEC>
-__global__ __launch_bounds__(kWsumBlock) void weighted_sum_kernel(RowTable rows, RowGroups groups,
-                                                                  const double* __restrict__ weights, int n,
-                                                                  int64_t nvec, int nt_result, float* __restrict__ out,
-                                                                  int tail) {
+__global__ __launch_bounds__(kTableBlock) void weighted_sum_kernel(RowTable rows, RowGroups groups,
+                                                                   const double* __restrict__ weights, int n,
+                                                                   int64_t nvec, float* __restrict__ out, int tail) {
   __shared__ const float* sel[BM_MAX_ROWS];
   __shared__ float wt[BM_MAX_ROWS];
   __shared__ double wd[BM_MAX_ROWS];
@@ -59,30 +58,7 @@ __global__ __launch_bounds__(kWsumBlock) void weighted_sum_kernel(RowTable rows,
   const int found = weighted_sum_prologue(rows, groups, weights, n, sel, wt, wd, &count);
   const int m = found < 0 ? 0 : found;
   const float init = found < 0 ? __builtin_nanf("") : 0.0f;  // a NaN weight: NaN everywhere, no row read
-  const int64_t nblk = (nvec + kWsumBlock - 1) / kWsumBlock;
-  for (int64_t b = blockIdx.x; b < nblk; b += gridDim.x) {
-    const int64_t v = b * kWsumBlock + threadIdx.x;
-    if (v >= nvec) continue;
-    float acc[VEC];
-#pragma unroll
-    for (int c = 0; c < VEC; ++c) acc[c] = init;
-#pragma unroll 8
-    for (int k = 0; k < m; ++k) {
-      float t[VEC];
-      load_stream<VEC>(sel[k] + v * VEC, t);
-      const float w = wt[k];
-#pragma unroll
-      for (int c = 0; c < VEC; ++c) acc[c] = __builtin_fmaf(w, t[c], acc[c]);
-    }
-    store_result_policy<VEC>(out + v * VEC, acc, nt_result);
-  }
-  // the d % VEC trailing columns: one lane each, in the last workgroup (no second launch)
-  if (VEC > 1 && blockIdx.x == gridDim.x - 1 && (int)threadIdx.x < tail) {
-    const int64_t j = nvec * VEC + threadIdx.x;
-    float acc = init;
-    for (int k = 0; k < m; ++k) acc = __builtin_fmaf(wt[k], sel[k][j], acc);
-    out[j] = acc;
-  }
+  table_sum_plain<VEC>(sel, m, nvec, tail, out, WeightedFold{wt, init});
 }
 
 }  // namespace bm
@@ -114,9 +90,9 @@ extern "C" int bm_weighted_sum(const float* const* rows, int n, const double* we
     float* const o = out + lo;
     const int vec = Alignment().of(t.p, n).of(o).vec();
     // (the dp % VEC trailing columns ride in the last workgroup of the body's launch: no launch of their own)
-    return for_body_and_tail<4>(Tail::kRidesNarrowed, vec, dp, kWsumBlock, caps_of(kWsumMaxBlocks), [&](auto width, const Span& sp) {
-      hipLaunchKernelGGL(weighted_sum_kernel<decltype(width)::value>, dim3(sp.grid), dim3(kWsumBlock), 0, s, t, grp,
-                         weights_dev, n, sp.count, 1, o, sp.tail);
+    return for_body_and_tail<4>(Tail::kRidesNarrowed, vec, dp, kTableBlock, caps_of(kWsumMaxBlocks), [&](auto width, const Span& sp) {
+      hipLaunchKernelGGL(weighted_sum_kernel<decltype(width)::value>, dim3(sp.grid), dim3(kTableBlock), 0, s, t, grp,
+                         weights_dev, n, sp.count, o, sp.tail);
       BM_LAUNCH_CHECK();
       return 0;
     });

@@ -165,3 +165,43 @@ def weighted_sum_reference(points, weights):
     total += term
     mass += np.abs(term)
   return total, (len(points) + 1) * 2.0 ** -24 * mass
+
+
+# The bit-for-bit cases of bm_weighted_sum (tests/test_gpu_weighted_sum.py): (rows, d, floats behind a 256-byte boundary,
+# seed).  "aliased": the stack of test_aliased_rows_are_one_group, 7 rows of which the last is referenced 5 times.
+WsumCase = collections.namedtuple("WsumCase", "name n d offset seed")
+WSUM_EXACT_CASES = (WsumCase("n11-align16", 11, 4099, 0, 11), WsumCase("n11-align8", 11, 4099, 2, 12),
+                    WsumCase("n11-align4", 11, 4099, 1, 13), WsumCase("n64", 64, 1027, 0, 64),
+                    WsumCase("aliased", 7, 4099, 0, 7), WsumCase("tail-only", 11, 3, 0, 3))
+
+
+def wsum_exact_inputs(case):
+  """(distinct float32 rows, stack: the index of the row behind each entry, float64 weights, one per entry)."""
+  rng = np.random.default_rng(case.seed)
+  rows = [rng.normal(size=case.d).astype(np.float32) for _ in range(case.n)]
+  stack = list(range(6)) + [6] * 5 if case.name == "aliased" else list(range(case.n))
+  weights = rng.uniform(0.01, 0.2, size=len(stack)) if case.name == "aliased" else rng.normal(size=len(stack))
+  return rows, stack, [float(w) for w in weights]
+
+
+def weighted_sum_exact(points, weights):
+  """The definition of bm_weighted_sum evaluated on the CPU: (float32 result, number of fused steps whose emulation met
+  a midpoint).  Weights of entries that are the same object are added in float64 in index order and rounded once to
+  fp32, groups of fp32 weight 0 are dropped, then acc = 0; acc = fma(w_k, x_k, acc) over the groups in index order.  The
+  fma is tests/first_pass_matrix.fma_emulated — exact except where its float64 sum is an fp32 midpoint, which the
+  second number counts: a case is usable bit for bit only when it is 0."""
+  import torch
+  from tests.first_pass_matrix import fma_emulated
+  groups = collections.OrderedDict()
+  for p, c in zip(points, weights):
+    groups.setdefault(id(p), [p, 0.0])
+    groups[id(p)][1] += float(c)
+  acc = torch.zeros(points[0].shape[0], dtype=torch.float32)
+  midpoints = 0
+  for p, c in groups.values():
+    w = np.float32(c)
+    if w == 0:
+      continue
+    acc, mid = fma_emulated(float(w), torch.from_numpy(p), 1.0, acc)
+    midpoints += int(mid.sum())
+  return acc.numpy(), midpoints

@@ -1,6 +1,7 @@
 """bm_weighted_sum on the GPU against a float64 sum: every vector width (row alignments of 4, 8 and 16 bytes), lengths
 that are no multiple of the width or of the block, more than one workgroup, 1 to 64 rows, aliased rows, weights that
-are exactly zero on NaN rows, negative weights, a NaN weight, and several launch pieces.
+are exactly zero on NaN rows, negative weights, a NaN weight, and several launch pieces; and bit for bit against the
+kernel's definition evaluated on the CPU (the same fused steps in the same order) on inputs where that evaluation is exact.
 Needs an MI355X: `pytest -m gpu`."""
 
 import math
@@ -30,6 +31,11 @@ def _rows(n, d, offset, seed):
   0: 16-byte aligned rows, 2: 8-byte, 1: 4-byte), and their host copies."""
   rng = np.random.default_rng(seed)
   host = [rng.normal(size=d).astype(np.float32) for _ in range(n)]
+  return _upload(host, offset), host
+
+
+def _upload(host, offset):
+  n, d = len(host), host[0].shape[0]
   per = -(-(d + offset) // 64) * 64
   pool = torch.zeros(n * per, dtype=torch.float32, device=DEV)
   dev = []
@@ -38,7 +44,7 @@ def _rows(n, d, offset, seed):
     view.copy_(torch.from_numpy(h))
     dev.append(view)
   assert all(v.data_ptr() % 16 == 4 * offset for v in dev)
-  return dev, host
+  return dev
 
 
 def _check(bm, dev, host, weights, tag):
@@ -61,6 +67,22 @@ def test_lengths_and_alignments(bm, d, offset):
   rng = np.random.default_rng(7 * d + offset)
   weights = list(rng.uniform(0.0, 1.0, size=11) / 5.5)
   _check(bm, dev, host, weights, (d, offset))
+
+
+@pytest.mark.parametrize("case", cc.WSUM_EXACT_CASES, ids=lambda c: c.name)
+def test_bit_for_bit(bm, case):
+  """Every coordinate against the kernel's definition evaluated on the CPU (cc.weighted_sum_exact): the same operations
+  in the same order, not only a sum inside a rounding bound.  tests/test_weighted_sum_cases_cpu.py proves that the
+  emulated fma meets no midpoint on these inputs, so no coordinate is left out."""
+  rows, stack, weights = cc.wsum_exact_inputs(case)
+  want, midpoints = cc.weighted_sum_exact([rows[i] for i in stack], weights)
+  assert midpoints == 0
+  dev = _upload(rows, case.offset)
+  out = bm.gars.weighted_sum([dev[i] for i in stack], torch.tensor(weights, dtype=torch.float64, device=DEV))
+  got = out.cpu().numpy()
+  assert got.dtype == np.float32 and got.shape == want.shape
+  differ = np.flatnonzero(got.view(np.uint32) != want.view(np.uint32))
+  assert differ.size == 0, (case.name, int(differ.size), int(differ[0]), float(got[differ[0]]), float(want[differ[0]]))
 
 
 @pytest.mark.parametrize("n", ROW_COUNTS)
