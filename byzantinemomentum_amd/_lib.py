@@ -193,6 +193,13 @@ SIGNATURES = {
                                               ctypes.c_void_p]),
   "bm_weighted_sum": (ctypes.c_int, [_c_float_pp, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                      ctypes.c_void_p]),
+  "bm_nnm_masks": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+  "bm_nnm_masks_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+  "bm_mix_rows": (ctypes.c_int, [_c_float_pp, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, _c_float_pp,
+                                 ctypes.c_void_p]),
+  "bm_colwise_mixed": (ctypes.c_int, [ctypes.c_int, _c_float_pp, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                      ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+  "bm_colwise_mixed_max_rows": (ctypes.c_int, []),
 }
 
 class Search(ctypes.Structure):

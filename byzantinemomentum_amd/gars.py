@@ -23,7 +23,8 @@ from . import _lib
 __all__ = ["median", "trmean", "phocas", "meamed", "krum", "bulyan", "brute", "aksel", "average", "cge",
            "krum_selection", "bulyan_ranking", "brute_selection", "aksel_selection", "cge_selection",
            "pairwise_sqdist", "rank_from_sqdist", "selected_mean", "bulyan_pass2", "aksel_sqdist",
-           "stable_argsort", "GarInputError", "geomed", "cclip", "center_weights", "weighted_sum"]
+           "stable_argsort", "GarInputError", "geomed", "cclip", "center_weights", "weighted_sum",
+           "nnm", "bucketing", "nnm_masks", "mix_rows", "nnm_rows", "colwise_mixed", "bucket_masks", "NNM_RULES"]
 
 
 class GarInputError(ValueError):
@@ -512,6 +513,149 @@ def cclip(gradients, f=None, tau=None, iters=3, tol=0.0, start=None, **kwargs):
   if tau is None:
     raise ValueError("cclip: tau (the clipping radius) is required")
   return _center("cclip", gradients, tau, iters, tol, start)
+
+
+# ---------------------------------------------------------------------------- #
+# Nearest-neighbour mixing and bucketing: one distance pass, the masks on the device, one mixing pass (or none: fused)
+
+def _check_masks(masks, count, where):
+  if (not isinstance(masks, torch.Tensor) or masks.dtype != torch.int64 or masks.dim() != 1 or masks.numel() < count
+      or not masks.is_contiguous()):
+    raise GarInputError(f"{where}: masks must be a contiguous int64 tensor of at least {count} words (bit j of word r: "
+                        "row j is averaged into output row r)")
+
+
+def nnm_masks(sq, n, f):
+  """The neighbour masks of nearest-neighbour mixing from the n x n float64 squared distances (bm_nnm_masks): word i has
+  bit j set iff row j is among the n - f rows nearest to row i, row i itself always included; ties to the lower index,
+  NaN distances last.  `sq` on the device (where pairwise_sqdist left it, possibly all-reduced): one workgroup, no
+  copy, no synchronisation; `sq` on the host: the host form, same masks.  Returns int64[MAX_ROWS] (the 64 bits of each
+  mask; zeros beyond n) where `sq` lives."""
+  n, f = int(n), int(f)
+  if not 1 <= n <= _lib.MAX_ROWS or not 0 <= f < n:
+    raise GarInputError(f"nnm: 1 <= n <= {_lib.MAX_ROWS} and 0 <= f < n are needed, got n = {n}, f = {f}")
+  if sq.dtype != torch.float64 or sq.numel() < n * n or not sq.is_contiguous():
+    raise GarInputError(f"nnm: expected a contiguous float64 matrix of {n} x {n} squared distances")
+  lib = _lib.load()
+  masks = torch.empty(_lib.MAX_ROWS, dtype=torch.int64, device=sq.device)
+  if not sq.is_cuda:
+    _lib.check(lib.bm_nnm_masks(_ptr(sq), n, f, _ptr(masks)), "bm_nnm_masks")
+    return masks
+  with torch.cuda.device(sq.device):
+    _lib.check(lib.bm_nnm_masks_device(_ptr(sq), n, f, _ptr(masks), _stream(sq.device)), "bm_nnm_masks_device")
+  return masks
+
+
+def mix_rows(gradients, masks, n_out):
+  """n_out averages over subsets of the gradients, from one read of them (bm_mix_rows): output row r is the sequential
+  float32 sum, in index order, of the gradients whose bit is set in masks[r] (a DEVICE int64 tensor), divided by their
+  count.  A gradient outside a mask is not read into that output; an empty mask gives a NaN row.  Returns a list of
+  n_out fresh tensors."""
+  n, d, device = _validate(gradients)
+  n_out = int(n_out)
+  if not 1 <= n_out <= _lib.MAX_ROWS:
+    raise GarInputError(f"mix_rows: 1 <= n_out <= {_lib.MAX_ROWS} is needed, got {n_out}")
+  _check_masks(masks, n_out, "mix_rows")
+  if masks.device != device:
+    raise GarInputError(f"mix_rows: the masks must be on {device}")
+  # one allocation, every row on a 256-byte boundary whatever d is: the widest stores the inputs allow
+  pool = torch.empty((n_out, -(-d // 64) * 64), dtype=torch.float32, device=device)
+  outs = [pool[r, :d] for r in range(n_out)]
+  if d == 0:
+    return outs
+  with torch.cuda.device(device):
+    _lib.check(_lib.load().bm_mix_rows(_lib.pointer_table(gradients), n, _ptr(masks), n_out, d, _lib.pointer_table(outs),
+                                       _stream(device)), "bm_mix_rows")
+  return outs
+
+
+def colwise_mixed(rule, gradients, masks, f=0):
+  """`rule` ("median" or "trmean") of the rows mix_rows(gradients, masks, n) would write, without writing them
+  (bm_colwise_mixed): same bits.  n <= bm_colwise_mixed_max_rows()."""
+  n, d, device = _validate(gradients)
+  _check_masks(masks, n, "colwise_mixed")
+  out = torch.empty(d, dtype=torch.float32, device=device)
+  if d == 0:
+    return out
+  op = {"median": _lib.OP_MEDIAN, "trmean": _lib.OP_TRMEAN}[rule]
+  with torch.cuda.device(device):
+    _lib.check(_lib.load().bm_colwise_mixed(op, _lib.pointer_table(gradients), n, _ptr(masks), d, int(f), _ptr(out),
+                                            _stream(device)), "bm_colwise_mixed")
+  return out
+
+
+def nnm_rows(gradients, f):
+  """The mixed rows of nearest-neighbour mixing: row i replaced by the mean of its n - f nearest rows, itself included
+  (one distance pass, the masks on the device, one mixing pass; no host synchronisation)."""
+  n, d, device = _validate(gradients)
+  return mix_rows(gradients, nnm_masks(pairwise_sqdist(gradients), n, f), n)
+
+
+# the rules nnm / bucketing can run on the mixed rows, and whether they take f
+NNM_RULES = {"median": False, "trmean": True, "phocas": True, "meamed": True, "krum": True, "bulyan": True, "brute": True,
+             "aksel": True, "cge": True, "average": False, "geomed": False, "cclip": False}
+
+
+def _rule_on(rule, rows, f, rule_args):
+  fn = globals()[rule]
+  return fn(rows, f=f, **rule_args) if NNM_RULES[rule] else fn(rows, **rule_args)
+
+
+def nnm(gradients, f, rule="trmean", **rule_args):
+  """Nearest-neighbour mixing, then `rule` on the mixed rows (NNM o rule of "Fixing by Mixing"): one distance pass, the
+  neighbour masks on the device, then
+    median / trmean up to bm_colwise_mixed_max_rows() rows: ONE kernel that mixes in registers and applies the rule (the
+      stack is read once, no mixed row is written);
+    otherwise: mix_rows, then the rule's own function on the mixed rows (rule_args are handed to it; `f` is the rule's f
+      as well).
+  No host synchronisation (graph-capturable) where the rule has none.  An unknown rule raises ValueError."""
+  if rule not in NNM_RULES:
+    raise ValueError(f"nnm: unknown rule {rule!r} ({', '.join(sorted(NNM_RULES))})")
+  n, d, device = _validate(gradients)
+  masks = nnm_masks(pairwise_sqdist(gradients), n, f)
+  if rule in ("median", "trmean") and not rule_args and n <= _lib.load().bm_colwise_mixed_max_rows():
+    return colwise_mixed(rule, gradients, masks, f if rule == "trmean" else 0)
+  return _rule_on(rule, mix_rows(gradients, masks, n), f, rule_args)
+
+
+def bucket_masks(n, s, perm):
+  """The ceil(n / s) masks of bucketing: bucket b holds perm[b s .. b s + s) (the last one may be smaller).  Host list of
+  Python integers."""
+  masks = []
+  for lo in range(0, n, s):
+    m = 0
+    for j in perm[lo:lo + s]:
+      m |= 1 << int(j)
+    masks.append(m)
+  return masks
+
+
+def _masks_tensor(masks, device):
+  """Python integers (64-bit patterns) as the int64 words the kernels read."""
+  return torch.tensor([m - (1 << 64) if m >= (1 << 63) else m for m in masks], dtype=torch.int64).to(device)
+
+
+def bucketing(gradients, s, rule, seed=None, perm=None, **rule_args):
+  """Bucketing (Karimireddy, He, Jaggi, ICLR 2022): the rows are shuffled, averaged in buckets of s, and `rule` runs on
+  the ceil(n / s) bucket means.  The permutation is drawn on the host (torch generator seeded with `seed`; None: the
+  global generator) or given as `perm`, a sequence holding 0 .. n-1 once each.  One mixing pass (mix_rows), then the
+  rule's own function.  The rule's `f` is the CALLER's business — pass it in rule_args: after bucketing at most f of the
+  ceil(n / s) means contain a Byzantine row, so the rule has to be admissible for that f on that many rows."""
+  if rule not in NNM_RULES:
+    raise ValueError(f"bucketing: unknown rule {rule!r} ({', '.join(sorted(NNM_RULES))})")
+  n, d, device = _validate(gradients)
+  s = int(s)
+  if not 1 <= s <= n:
+    raise ValueError(f"bucketing: the bucket size must be within 1..{n}, got {s}")
+  if perm is None:
+    gen = None if seed is None else torch.Generator().manual_seed(int(seed))
+    perm = torch.randperm(n, generator=gen).tolist()
+  perm = [int(j) for j in perm]
+  if sorted(perm) != list(range(n)):
+    raise ValueError(f"bucketing: perm must hold 0..{n - 1} once each")
+  masks = bucket_masks(n, s, perm)
+  means = mix_rows(gradients, _masks_tensor(masks, device), len(masks))
+  return globals()[rule](means, **rule_args)
 
 
 def cge_selection(gradients, f, **kwargs):

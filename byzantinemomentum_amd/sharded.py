@@ -113,7 +113,7 @@ class HipBackend:
   capabilities = frozenset((
     "step_worker", "momentum_stats_colwise", "momentum_stats_sqdist", "stack_stats_colwise", "stack_stats_sqdist",
     "device_search", "attack_ranking_device", "bulyan_pass2_eval", "order_pair", "colwise_eval", "sqdist2", "anticge",
-    "accept_count", "attack_vector", "center_weights", "weighted_sum"))
+    "accept_count", "attack_vector", "center_weights", "weighted_sum", "nnm_masks", "mix_rows", "colwise_mixed"))
 
   def __init__(self):
     from . import gars, stats
@@ -158,6 +158,20 @@ class HipBackend:
 
   def weighted_sum(self, gradients, weights):
     return self.gars.weighted_sum(gradients, weights)
+
+  def nnm_masks(self, sq, n, f):
+    """The neighbour masks of nearest-neighbour mixing from the (all-reduced) squared distances, where they are
+    (bm_nnm_masks_device: one workgroup, no synchronisation): int64[MAX_ROWS]."""
+    return self.gars.nnm_masks(sq, n, f)
+
+  def mix_rows(self, gradients, masks, n_out):
+    return self.gars.mix_rows(gradients, masks, n_out)
+
+  def colwise_mixed_max_rows(self):
+    return _lib.load().bm_colwise_mixed_max_rows()
+
+  def colwise_mixed(self, rule, gradients, masks, f):
+    return self.gars.colwise_mixed(rule, gradients, masks, f)
 
   def sharded_rule(self, name, comm, gradients, f, m, d_total=None, with_order=False):
     """Multi-Krum / Bulyan of the local slice in one C call (bm_sharded_krum / bm_sharded_bulyan);
@@ -385,6 +399,35 @@ def _weighted_sum_torch(points, weights):
   return acc.to(points[0].dtype)
 
 
+def _nnm_masks_torch(sq, n, f):
+  """bm_nnm_masks in plain torch (fp64 ranking, where `sq` lives) for a backend without the kernel: row i and the
+  n - f - 1 other rows of smallest distance, ties to the lower index, NaN last (a stable sort) — int64[MAX_ROWS]."""
+  D = sq[:n, :n].to(torch.float64)
+  words = []
+  for i in range(n):
+    others = [j for j in range(n) if j != i]
+    order = torch.sort(D[i, others], stable=True).indices.tolist()  # NaN sorts last, equal keys keep their order
+    word = 1 << i
+    for t in order[:n - f - 1]:
+      word |= 1 << others[t]
+    words.append(word - (1 << 64) if word >= (1 << 63) else word)
+  return torch.tensor(words + [0] * (_lib.MAX_ROWS - n), dtype=torch.int64, device=sq.device)
+
+
+def _mix_rows_torch(rows, masks, n_out):
+  """bm_mix_rows in plain torch: per output row the sequential fp32 sum, in index order, of the rows in its mask, then
+  one division by their count.  A row outside the mask is not touched; an empty mask gives NaN."""
+  n = len(rows)
+  outs = []
+  for word in masks[:n_out].tolist():
+    members = [j for j in range(n) if (word >> j) & 1]
+    acc = torch.zeros_like(rows[0])
+    for j in members:
+      acc = acc + rows[j]
+    outs.append(acc / torch.tensor(float(len(members)), dtype=rows[0].dtype, device=rows[0].device))
+  return outs
+
+
 class ShardedAggregator:
   """Aggregation rules over gradients whose coordinates are sharded across the ranks of `group`."""
 
@@ -421,6 +464,7 @@ class ShardedAggregator:
     # info (iterations run, move^2, usable rows)
     self.last_weights = None
     self.last_center_info = None
+    self.last_masks = None   # the neighbour masks of the latest nnm of THIS aggregator (int64[MAX_ROWS])
     self._total = None       # (length of the whole vectors, this rank's shard length when it was determined)
 
   def shard_rows(self, rows, d=None):
@@ -716,6 +760,41 @@ class ShardedAggregator:
     if tau is None:
       raise ValueError("cclip: tau (the clipping radius) is required")
     return self._center("cclip", local, tau, iters, tol, start, d_total)
+
+  NNM_RULES = ("median", "trmean", "phocas", "meamed", "krum", "bulyan", "brute", "aksel", "cge", "average", "geomed",
+               "cclip")
+
+  def nnm(self, local, f, rule="trmean", d_total=None, **rule_args):
+    """Nearest-neighbour mixing, then `rule` on the mixed rows (gars.nnm), on this rank's slice: (1) the squared
+    distances, all-reduced — the neighbours are those of the WHOLE vectors, the same masks on every rank; (2) mixing and
+    a coordinate-wise rule are column-local: the fused kernel for median / trmean where the backend has it, else the
+    mixed slice is written and the aggregator's own rule runs on it (a distance-based rule then all-reduces the
+    distances of the mixed rows).  A backend that declares the "nnm_masks" / "mix_rows" / "colwise_mixed" capabilities
+    runs the kernels; any other gets the same steps in plain torch (fp64 ranking, sequential fp32 sums).
+    `self.last_masks` keeps the masks (int64[MAX_ROWS])."""
+    from . import gars
+    if rule not in self.NNM_RULES:
+      raise ValueError(f"nnm: unknown rule {rule!r} ({', '.join(sorted(self.NNM_RULES))})")
+    rows = list(local)
+    n = len(rows)
+    if not 1 <= n <= _lib.MAX_ROWS or not 0 <= f < n:
+      raise gars.GarInputError(f"nnm: 1 <= n <= {_lib.MAX_ROWS} and 0 <= f < n are needed, got n = {n}, f = {f}")
+    caps = getattr(self.backend, "capabilities", ())
+    total = self._total_of(local, d_total)
+    sq = self.global_sqdist(rows, total)
+    masks = self.backend.nnm_masks(sq, n, f) if "nnm_masks" in caps else _nnm_masks_torch(sq, n, f)
+    self.last_masks = masks
+    if (rule in ("median", "trmean") and not rule_args and "colwise_mixed" in caps
+        and n <= self.backend.colwise_mixed_max_rows()):
+      return self.backend.colwise_mixed(rule, rows, masks, f if rule == "trmean" else 0)
+    mixed = self.backend.mix_rows(rows, masks, n) if "mix_rows" in caps else _mix_rows_torch(rows, masks, n)
+    mixed = Shards(mixed, d_total=total)
+    fn = getattr(self, rule)
+    if rule in ("median", "average"):
+      return fn(mixed, **rule_args)
+    if rule in ("krum", "bulyan", "brute", "geomed", "cclip"):
+      rule_args.setdefault("d_total", total)
+    return fn(mixed, f, **rule_args)
 
   def anticge(self, local_honests, f_decl, f_real):
     """The reference's `anticge` attack (attacks/anticge.py:49-78) on this rank's slice of the honest gradients:

@@ -584,6 +584,39 @@ int bm_center_weights_device(const double* sq_dev, int n, int has_start, int mod
  * launches nothing. */
 int bm_weighted_sum(const float* const* rows, int n, const double* weights_dev, int64_t d, float* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Nearest-neighbour mixing (Allouah, Farhadkhani, Guerraoui, Gupta, Pinot, Stephan, "Fixing by Mixing", AISTATS 2023):
+ * every row is replaced by the average of its k = n - f nearest rows, itself included, and any rule runs on the mixed
+ * rows.  These five entry points joined ABI 23: additions only, no signature changed.  Not in the reference.
+ *
+ * Neighbour masks, from the n x n fp64 squared distances D (bm_pairwise_sqdist), 1 <= n <= BM_MAX_ROWS, 0 <= f < n:
+ * N_i holds row i itself, whatever D[i][i] is, and the k - 1 OTHER rows of smallest D[i][j]; ties go to the lower
+ * index; NaN keys sort last, in index order among themselves (+inf before NaN).  masks[i] has bit j set iff j is in
+ * N_i: one 64-bit word per row of the mixing matrix.  BM_MAX_ROWS masks are written, zeros beyond n.
+ * bm_nnm_masks: HOST function on a HOST matrix, no stream.  bm_nnm_masks_device: the same on the DEVICE matrix, one
+ * workgroup, no copy, no synchronisation; the same masks.  Both return BM_EINVAL for a bad n or f before any HIP call. */
+int bm_nnm_masks(const double* sq_host, int n, int f, uint64_t* masks_host);
+int bm_nnm_masks_device(const double* sq_dev, int n, int f, uint64_t* masks_dev, void* stream);
+
+/* Mixing: n_out averages over subsets of the n rows, 1 <= n_out <= BM_MAX_ROWS (masks_dev: DEVICE, n_out words; the
+ * masks above, or one mask per bucket: bucketing).  Per coordinate and output row r:
+ *     acc = +0.0f;  for j = 0 .. n-1 ascending, bit j of masks[r] set:  acc = acc + rows[j] (fp32);
+ *     out_rows[r] = acc / (float)popcount(masks[r])     one IEEE division
+ * Bits at positions >= n are ignored; an empty mask gives NaN (0 / 0); a row outside the mask does not influence the
+ * result even where it holds NaN or inf.  One streaming pass: every column is read once, 4 d (n + n_out) bytes.
+ * rows may alias one another; every out_rows[r] must be disjoint from the other outputs and from every input, else
+ * BM_EINVAL.  d == 0 launches nothing. */
+int bm_mix_rows(const float* const* rows, int n, const uint64_t* masks_dev, int n_out, int64_t d, float* const* out_rows,
+                void* stream);
+
+/* out = rule(y_0 .. y_{n-1}), y_r the mixed rows of bm_mix_rows with n_out = n (masks_dev: at least n words), for op =
+ * BM_OP_MEDIAN or BM_OP_TRMEAN (f: the trimmed mean's, n >= 2 f + 1), without writing a mixed row: 4 d (n + 1) bytes.
+ * The same bits as bm_colwise on the rows bm_mix_rows writes.  Any other op, or n above bm_colwise_mixed_max_rows(),
+ * returns BM_EINVAL: the caller then runs bm_mix_rows and bm_colwise. */
+int bm_colwise_mixed(int op, const float* const* rows, int n, const uint64_t* masks_dev, int64_t d, int f, float* out,
+                     void* stream);
+int bm_colwise_mixed_max_rows(void);
+
 #ifdef __cplusplus
 }
 #endif

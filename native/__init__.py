@@ -172,6 +172,37 @@ def register_center_rules():
   return ["native-geomed", "native-cclip"]
 
 
+_nnm_registered = False
+
+
+def _nnm_rule(rule):
+  def aggregate(gradients, f, **kwargs):
+    return _gars.nnm(gradients, f, rule=rule, **kwargs)
+  aggregate.__name__ = f"nnm_{rule}"
+  aggregate.__doc__ = f"Nearest-neighbour mixing, then {rule} on the mixed rows (byzantinemomentum_amd.gars.nnm)"
+  return aggregate
+
+
+def register_nnm_rules():
+  """Register `native-nnm-<rule>` for every rule of byzantinemomentum_amd.gars.NNM_RULES with the reference's registry:
+  nearest-neighbour mixing (each gradient replaced by the mean of its n - f nearest, itself included), then the rule on
+  the mixed rows (`--gar native-nnm-trmean`, `--gar native-nnm-krum --gar-args m:1`).  NOT done at import, like
+  register_center_rules(): the names `import aggregators` registers by itself stay the reference's own rule set.  The
+  generic validator; no `influence` (a mixed row has no single owner whose selection could be counted).  Returns the
+  names registered."""
+  global _nnm_registered
+  agg = sys.modules.get("aggregators")
+  register = getattr(agg, "register", None)
+  if register is None or not hasattr(agg, "gars"):
+    raise RuntimeError("native.register_nnm_rules() needs the reference's `aggregators` package imported first")
+  names = ["native-nnm-" + rule for rule in _gars.NNM_RULES]
+  if not _nnm_registered:
+    _nnm_registered = True
+    for rule in _gars.NNM_RULES:
+      register("native-nnm-" + rule, _nnm_rule(rule), _generic_check())
+  return names
+
+
 _bound = False
 
 
