@@ -24,7 +24,8 @@ __all__ = ["median", "trmean", "phocas", "meamed", "krum", "bulyan", "brute", "a
            "krum_selection", "bulyan_ranking", "brute_selection", "aksel_selection", "cge_selection",
            "pairwise_sqdist", "rank_from_sqdist", "selected_mean", "bulyan_pass2", "aksel_sqdist",
            "stable_argsort", "GarInputError", "geomed", "cclip", "center_weights", "weighted_sum",
-           "nnm", "bucketing", "nnm_masks", "mix_rows", "nnm_rows", "colwise_mixed", "bucket_masks", "NNM_RULES"]
+           "nnm", "bucketing", "nnm_masks", "mix_rows", "nnm_rows", "colwise_mixed", "bucket_masks", "NNM_RULES",
+           "mixed_sqdist", "mix_weights", "SCALAR_RULES"]
 
 
 class GarInputError(ValueError):
@@ -601,17 +602,192 @@ def _rule_on(rule, rows, f, rule_args):
   return fn(rows, f=f, **rule_args) if NNM_RULES[rule] else fn(rows, **rule_args)
 
 
-def nnm(gradients, f, rule="trmean", **rule_args):
+# ---------------------------------------------------------------------------- #
+# The distance-based rules on mixed rows from scalars: no mixed row is written (form="scalars" of nnm / bucketing)
+
+def _mask_words(masks, count, device, where):
+  """`masks` as the int64 words the entry points read, where `device` is: a tensor is checked, a sequence of Python
+  integers (bucket_masks) is converted."""
+  if not isinstance(masks, torch.Tensor):
+    masks = _masks_tensor([int(m) for m in masks], device)
+  _check_masks(masks, count, where)
+  if masks.device != device:
+    raise GarInputError(f"{where}: the masks must be on {device}")
+  return masks
+
+
+def mixed_sqdist(sq, n_in, masks, n_out):
+  """The n_out x n_out float64 squared distances between the rows mix_rows(gradients, masks, n_out) would write, from the
+  n_in x n_in squared distances `sq` of the gradients alone (bm_mixed_sqdist): no mixed row exists.  Equal masks give
+  exactly 0, an empty mask NaN in its row and column, a non-finite distance read for a pair NaN.  `sq` on the device
+  (where pairwise_sqdist left it, possibly all-reduced): one workgroup, no copy, no synchronisation — a mask with a bit
+  at or above n_in then gives NaN everywhere; `sq` on the host: the host form, same bits, and such a mask is refused.
+  `masks`: an int64 tensor where `sq` lives (nnm_masks), or a sequence of Python integers (bucket_masks)."""
+  n_in, n_out = int(n_in), int(n_out)
+  if not 1 <= n_in <= _lib.MAX_ROWS or not 1 <= n_out <= _lib.MAX_ROWS:
+    raise GarInputError(f"mixed_sqdist: 1 <= n_in, n_out <= {_lib.MAX_ROWS} is needed, got {n_in}, {n_out}")
+  if (not isinstance(sq, torch.Tensor) or sq.dtype != torch.float64 or sq.numel() < n_in * n_in
+      or not sq.is_contiguous()):
+    raise GarInputError(f"mixed_sqdist: expected a contiguous float64 matrix of {n_in} x {n_in} squared distances")
+  masks = _mask_words(masks, n_out, sq.device, "mixed_sqdist")
+  lib = _lib.load()
+  out = torch.empty((n_out, n_out), dtype=torch.float64, device=sq.device)
+  if not sq.is_cuda:
+    _lib.check(lib.bm_mixed_sqdist(_ptr(sq), n_in, _ptr(masks), n_out, _ptr(out)), "bm_mixed_sqdist")
+    return out
+  with torch.cuda.device(sq.device):
+    _lib.check(lib.bm_mixed_sqdist_device(_ptr(sq), n_in, _ptr(masks), n_out, _ptr(out), _stream(sq.device)),
+               "bm_mixed_sqdist_device")
+  return out
+
+
+def mix_weights(masks, n_in, n_out, weights=None, selection=None, m=None):
+  """The weights of the ORIGINAL rows behind a weighted sum of mixed rows (bm_mix_weights): float64[MAX_ROWS], zeros
+  beyond n_in — what weighted_sum reads.  Exactly one of
+    weights    float64 tensor of at least n_out entries (center_weights), or
+    selection  int32 tensor whose first m entries name the mixed rows that are averaged (a ranking, a Brute subset): 1 / m
+               each, duplicates add up, an entry outside 0 .. n_out-1 gives NaN everywhere.
+  `masks`: an int64 tensor (host or device: the host or the device form, same bits) or a sequence of Python integers,
+  which goes where the weights / the selection live."""
+  n_in, n_out = int(n_in), int(n_out)
+  if not 1 <= n_in <= _lib.MAX_ROWS or not 1 <= n_out <= _lib.MAX_ROWS:
+    raise GarInputError(f"mix_weights: 1 <= n_in, n_out <= {_lib.MAX_ROWS} is needed, got {n_in}, {n_out}")
+  if (weights is None) == (selection is None):
+    raise ValueError("mix_weights: exactly one of weights and selection is needed")
+  given = weights if weights is not None else selection
+  if not isinstance(given, torch.Tensor) or given.dim() != 1 or not given.is_contiguous():
+    raise GarInputError("mix_weights: weights / selection must be a contiguous 1-D tensor")
+  masks = _mask_words(masks, n_out, given.device, "mix_weights")
+  if weights is not None:
+    if weights.dtype != torch.float64 or weights.numel() < n_out:
+      raise GarInputError(f"mix_weights: weights must be a float64 tensor of at least {n_out} entries")
+    m = 0
+  else:
+    if m is None:
+      raise ValueError("mix_weights: m (how many entries of the selection are averaged) is needed")
+    m = int(m)
+    if not 1 <= m <= _lib.MAX_ROWS:
+      raise GarInputError(f"mix_weights: 1 <= m <= {_lib.MAX_ROWS} is needed, got {m}")
+    if selection.dtype != torch.int32 or selection.numel() < m:
+      raise GarInputError(f"mix_weights: selection must be an int32 tensor of at least {m} entries")
+  lib = _lib.load()
+  out = torch.empty(_lib.MAX_ROWS, dtype=torch.float64, device=given.device)
+  args = (_ptr(masks), n_in, n_out, None if weights is None else _ptr(weights),
+          None if selection is None else _ptr(selection), m, _ptr(out))
+  if not given.is_cuda:
+    _lib.check(lib.bm_mix_weights(*args), "bm_mix_weights")
+    return out
+  with torch.cuda.device(given.device):
+    _lib.check(lib.bm_mix_weights_device(*args, _stream(given.device)), "bm_mix_weights_device")
+  return out
+
+
+# the rules form="scalars" serves: their output on mixed rows needs the distances between mixed rows and a weighted sum
+# of the original rows, nothing else
+SCALAR_RULES = ("krum", "brute", "geomed", "cclip", "average")
+FORMS = ("rows", "scalars")
+
+
+def _check_form(where, form, rule):
+  if form not in FORMS:
+    raise ValueError(f"{where}: unknown form {form!r} ({', '.join(FORMS)})")
+  if form == "scalars" and rule not in SCALAR_RULES:
+    raise ValueError(f"{where}: form='scalars' serves {', '.join(SCALAR_RULES)} only, got rule {rule!r}")
+
+
+def _rule_on_scalars(where, gradients, rule, n_out, masks_from, need_sq, rule_args):
+  """`rule` on the n_out mixed rows of `gradients` without writing one: distances of the ORIGINAL rows (and of a cclip
+  start, point n) -> masks_from(that n x n matrix, or None when neither the masks nor the rule read distances) ->
+  mixed_sqdist -> the rule's own scalar stage -> mix_weights -> weighted_sum.  Launches on the current stream only;
+  the one synchronisation is brute's with check=True.  The result carries `mix_masks`, `mix_weights` and, for krum and
+  brute, `mix_selection` = (index tensor, count)."""
+  global last_brute_status
+  n, d, device = _validate(gradients)
+  args = dict(rule_args)
+  takes_f = NNM_RULES[rule]
+  if takes_f and "f" not in args:
+    raise TypeError(f"{where}: {rule} needs f (the rule's f on the {n_out} mixed rows)")
+  f = args.pop("f", None)
+  points, start, selection = list(gradients), None, None
+  if rule in ("geomed", "cclip"):
+    mode = rule
+    if rule == "geomed":
+      param, iters = args.pop("nu", 1e-6), args.pop("iters", 8)
+    else:
+      param, iters, start = args.pop("tau", None), args.pop("iters", 3), args.pop("start", None)
+      if param is None:
+        raise ValueError("cclip: tau (the clipping radius) is required")
+    tol = args.pop("tol", 0.0)
+    check_center_args(mode, param, iters, tol)
+    if start is not None:
+      points.append(start)
+      if n_out + 1 > _lib.MAX_ROWS or n + 1 > _lib.MAX_ROWS:
+        raise GarInputError(f"cclip: at most {_lib.MAX_ROWS - 1} gradients are supported with a start vector, got {n}")
+      _validate(points)
+  sq = None
+  if need_sq or rule != "average":
+    sq = pairwise_sqdist(points)
+  masks = masks_from(sq if start is None or sq is None else sq[:n, :n].contiguous())
+  n_in = len(points)
+  if start is not None:  # the start is point n of the pass and mixed row n_out, alone in its mask
+    own = torch.full((1,), (1 << n) - (1 << 64 if n == 63 else 0), dtype=torch.int64, device=device)
+    masks = torch.cat((masks[:n_out], own))
+  if rule == "average":
+    weights = torch.full((_lib.MAX_ROWS,), 1.0 / n_out, dtype=torch.float64, device=device)
+    w = mix_weights(masks, n_in, n_out, weights=weights)
+  else:
+    mixed = mixed_sqdist(sq, n_in, masks, n_out + (start is not None))
+    if rule == "krum":
+      m = args.pop("m", None)
+      if m is None:
+        m = n_out - f - 2
+      order, _ = rank_from_sqdist(mixed, n_out, f, m, _lib.RANK_KRUM)
+      selection = (order, m)
+    elif rule == "brute":
+      sel, status = brute_select_device(mixed, n_out, f)
+      last_brute_status = status
+      if args.pop("check", False) and not torch.cuda.is_current_stream_capturing():
+        code = int(status.item())
+        if code == -2:  # the device search gave up: the host search has no budget
+          table = torch.zeros(_lib.MAX_ROWS, dtype=torch.int32)
+          table[:n_out - f] = torch.tensor(brute_select_host(mixed.sqrt().cpu().contiguous(), n_out, f), dtype=torch.int32)
+          sel, status = table.to(device), torch.zeros(1, dtype=torch.int32, device=device)
+          last_brute_status = status
+        elif code != 0:
+          raise RuntimeError(BRUTE_NO_SUBSET)
+      selection = (sel, n_out - f)
+    if selection is not None:
+      w = mix_weights(masks, n_in, n_out, selection=selection[0], m=selection[1])
+    else:
+      weights, _ = center_weights(mixed, n_out, mode, param, iters, tol, start is not None)
+      w = mix_weights(masks, n_in, n_out + (start is not None), weights=weights)
+  out = weighted_sum(points, w)
+  out.mix_masks, out.mix_weights, out.mix_selection = masks, w, selection
+  if rule == "brute":
+    out.brute_status = status
+  return out
+
+
+def nnm(gradients, f, rule="trmean", form="rows", **rule_args):
   """Nearest-neighbour mixing, then `rule` on the mixed rows (NNM o rule of "Fixing by Mixing"): one distance pass, the
   neighbour masks on the device, then
     median / trmean up to bm_colwise_mixed_max_rows() rows: ONE kernel that mixes in registers and applies the rule (the
       stack is read once, no mixed row is written);
     otherwise: mix_rows, then the rule's own function on the mixed rows (rule_args are handed to it; `f` is the rule's f
       as well).
+  form="scalars" (krum, brute, geomed, cclip, average: SCALAR_RULES; any other rule raises ValueError) writes no mixed
+  row either: the distances between mixed rows come from the distance matrix the masks were made of (mixed_sqdist), the
+  rule's scalar stage runs on them, and its output is ONE weighted sum of the original rows (mix_weights, weighted_sum) —
+  the same selection as form="rows" wherever the rule's decisions are not within the distance pass's error of a tie.
   No host synchronisation (graph-capturable) where the rule has none.  An unknown rule raises ValueError."""
   if rule not in NNM_RULES:
     raise ValueError(f"nnm: unknown rule {rule!r} ({', '.join(sorted(NNM_RULES))})")
+  _check_form("nnm", form, rule)
   n, d, device = _validate(gradients)
+  if form == "scalars":
+    if NNM_RULES[rule]:
+      rule_args = dict(rule_args, f=f)
+    return _rule_on_scalars("nnm", gradients, rule, n, lambda sq: nnm_masks(sq, n, f), True, rule_args)
   masks = nnm_masks(pairwise_sqdist(gradients), n, f)
   if rule in ("median", "trmean") and not rule_args and n <= _lib.load().bm_colwise_mixed_max_rows():
     return colwise_mixed(rule, gradients, masks, f if rule == "trmean" else 0)
@@ -635,14 +811,17 @@ def _masks_tensor(masks, device):
   return torch.tensor([m - (1 << 64) if m >= (1 << 63) else m for m in masks], dtype=torch.int64).to(device)
 
 
-def bucketing(gradients, s, rule, seed=None, perm=None, **rule_args):
+def bucketing(gradients, s, rule, seed=None, perm=None, form="rows", **rule_args):
   """Bucketing (Karimireddy, He, Jaggi, ICLR 2022): the rows are shuffled, averaged in buckets of s, and `rule` runs on
   the ceil(n / s) bucket means.  The permutation is drawn on the host (torch generator seeded with `seed`; None: the
   global generator) or given as `perm`, a sequence holding 0 .. n-1 once each.  One mixing pass (mix_rows), then the
   rule's own function.  The rule's `f` is the CALLER's business — pass it in rule_args: after bucketing at most f of the
-  ceil(n / s) means contain a Byzantine row, so the rule has to be admissible for that f on that many rows."""
+  ceil(n / s) means contain a Byzantine row, so the rule has to be admissible for that f on that many rows.
+  form="scalars" (SCALAR_RULES only) writes no bucket mean: one distance pass over the rows (none for "average"), the
+  rule's scalar stage on the distances between the means (mixed_sqdist), one weighted sum of the rows."""
   if rule not in NNM_RULES:
     raise ValueError(f"bucketing: unknown rule {rule!r} ({', '.join(sorted(NNM_RULES))})")
+  _check_form("bucketing", form, rule)
   n, d, device = _validate(gradients)
   s = int(s)
   if not 1 <= s <= n:
@@ -654,6 +833,9 @@ def bucketing(gradients, s, rule, seed=None, perm=None, **rule_args):
   if sorted(perm) != list(range(n)):
     raise ValueError(f"bucketing: perm must hold 0..{n - 1} once each")
   masks = bucket_masks(n, s, perm)
+  if form == "scalars":
+    return _rule_on_scalars("bucketing", gradients, rule, len(masks), lambda sq: _masks_tensor(masks, device), False,
+                            rule_args)
   means = mix_rows(gradients, _masks_tensor(masks, device), len(masks))
   return globals()[rule](means, **rule_args)
 

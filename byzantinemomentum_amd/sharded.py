@@ -113,7 +113,8 @@ class HipBackend:
   capabilities = frozenset((
     "step_worker", "momentum_stats_colwise", "momentum_stats_sqdist", "stack_stats_colwise", "stack_stats_sqdist",
     "device_search", "attack_ranking_device", "bulyan_pass2_eval", "order_pair", "colwise_eval", "sqdist2", "anticge",
-    "accept_count", "attack_vector", "center_weights", "weighted_sum", "nnm_masks", "mix_rows", "colwise_mixed"))
+    "accept_count", "attack_vector", "center_weights", "weighted_sum", "nnm_masks", "mix_rows", "colwise_mixed",
+    "mixed_sqdist", "mix_weights"))
 
   def __init__(self):
     from . import gars, stats
@@ -166,6 +167,14 @@ class HipBackend:
 
   def mix_rows(self, gradients, masks, n_out):
     return self.gars.mix_rows(gradients, masks, n_out)
+
+  def mixed_sqdist(self, sq, n_in, masks, n_out):
+    """The squared distances between mixed rows from the (all-reduced) distances of the rows, where they are
+    (bm_mixed_sqdist_device: one workgroup, no synchronisation): fp64 (n_out, n_out)."""
+    return self.gars.mixed_sqdist(sq, n_in, masks, n_out)
+
+  def mix_weights(self, masks, n_in, n_out, weights=None, selection=None, m=None):
+    return self.gars.mix_weights(masks, n_in, n_out, weights=weights, selection=selection, m=m)
 
   def colwise_mixed_max_rows(self):
     return _lib.load().bm_colwise_mixed_max_rows()
@@ -426,6 +435,83 @@ def _mix_rows_torch(rows, masks, n_out):
       acc = acc + rows[j]
     outs.append(acc / torch.tensor(float(len(members)), dtype=rows[0].dtype, device=rows[0].device))
   return outs
+
+
+def _mask_words(masks, count):
+  return [int(w) & ((1 << 64) - 1) for w in masks[:count].tolist()]
+
+
+def _mixed_sqdist_torch(sq, n_in, masks, n_out):
+  """bm_mixed_sqdist for a backend without the kernel: the definition of include/bm_gar.h walked in Python floats (IEEE
+  doubles, the sums in the stated order), so the host form's bits — fp64 (n_out, n_out) where `sq` lives.  Reads the
+  matrix and the masks on the host."""
+  D = sq.reshape(-1)[:n_in * n_in].view(n_in, n_in).tolist()
+  words = _mask_words(masks, n_out)
+  if any(w >> n_in for w in words):
+    raise ValueError(f"mixed_sqdist: a mask has a bit at or above n_in = {n_in}")
+  members = [[j for j in range(n_in) if (w >> j) & 1] for w in words]
+  Q = [[0.0] * n_out for _ in range(n_in)]
+  for i in range(n_in):
+    for b in range(n_out):
+      s = 0.0
+      for j in members[b]:
+        if j != i:
+          s = s + D[min(i, j)][max(i, j)]
+      Q[i][b] = s
+
+  def P(a, b):
+    s = 0.0
+    for i in members[a]:
+      s = s + Q[i][b]
+    return s
+
+  diag = [P(a, a) for a in range(n_out)]
+  out = [[0.0] * n_out for _ in range(n_out)]
+  for a in range(n_out):
+    out[a][a] = 0.0 if words[a] else math.nan
+    for b in range(a + 1, n_out):
+      if not words[a] or not words[b]:
+        v = math.nan
+      elif words[a] == words[b]:
+        v = 0.0
+      else:
+        x, y = (a, b) if words[a] < words[b] else (b, a)  # the smaller mask word walks the outer sum
+        p, cx, cy = P(x, y), float(len(members[x])), float(len(members[y]))
+        if not (math.isfinite(p) and math.isfinite(diag[x]) and math.isfinite(diag[y])):
+          v = math.nan
+        else:
+          v = p / (cx * cy) - 0.5 * diag[x] / (cx * cx) - 0.5 * diag[y] / (cy * cy)
+          v = 0.0 if v <= 0.0 else v
+      out[a][b] = out[b][a] = v
+  return torch.tensor(out, dtype=torch.float64, device=sq.device)
+
+
+def _mix_weights_torch(masks, n_in, n_out, weights=None, selection=None, m=None):
+  """bm_mix_weights for a backend without the kernel, in Python floats: the host form's bits — fp64[MAX_ROWS] where the
+  weights / the selection live."""
+  given = weights if weights is not None else selection
+  words = _mask_words(masks, n_out)
+  if any(w >> n_in for w in words):
+    raise ValueError(f"mix_weights: a mask has a bit at or above n_in = {n_in}")
+  ok = True
+  if selection is not None:
+    sel = [int(t) for t in selection[:m].tolist()]
+    ok = all(0 <= t < n_out for t in sel)
+    w = [0.0] * n_out
+    if ok:
+      for t in sel:
+        w[t] = w[t] + 1.0 / float(m)
+  else:
+    w = weights[:n_out].tolist()
+  ok = ok and all(w[r] == 0.0 or words[r] for r in range(n_out))
+  out = [0.0] * _lib.MAX_ROWS
+  for j in range(n_in):
+    s = 0.0
+    for r in range(n_out):
+      if w[r] != 0.0 and (words[r] >> j) & 1:
+        s = s + w[r] / float(bin(words[r]).count("1"))
+    out[j] = s if ok else math.nan
+  return torch.tensor(out, dtype=torch.float64, device=given.device)
 
 
 class ShardedAggregator:
@@ -764,23 +850,107 @@ class ShardedAggregator:
   NNM_RULES = ("median", "trmean", "phocas", "meamed", "krum", "bulyan", "brute", "aksel", "cge", "average", "geomed",
                "cclip")
 
-  def nnm(self, local, f, rule="trmean", d_total=None, **rule_args):
+  SCALAR_RULES = ("krum", "brute", "geomed", "cclip", "average")
+
+  def _nnm_scalars(self, rows, f, rule, total, rule_args):
+    """form="scalars" of nnm: (1) the squared distances of the rows (+ a cclip start as point n), all-reduced — the ONE
+    collective; (2) on every rank from that matrix, hence with the same bits: the neighbour masks, the distances
+    between the mixed rows (mixed_sqdist), the rule's scalar stage, the weights of the original rows (mix_weights);
+    (3) the weighted sum of the local slice.  No mixed row is written and no second matrix is reduced.  A backend that
+    declares the "mixed_sqdist" / "mix_weights" capabilities runs those as kernels; any other gets them in plain
+    Python floats (fp64, the host form's bits)."""
+    from . import gars
+    caps = getattr(self.backend, "capabilities", ())
+    n = len(rows)
+    args = dict(rule_args)
+    args.pop("d_total", None)
+    start, mode = None, rule if rule in ("geomed", "cclip") else None
+    if mode == "geomed":
+      param, iters = args.pop("nu", 1e-6), args.pop("iters", 8)
+    elif mode == "cclip":
+      param, iters, start = args.pop("tau", None), args.pop("iters", 3), args.pop("start", None)
+      if param is None:
+        raise ValueError("cclip: tau (the clipping radius) is required")
+    if mode is not None:
+      tol = args.pop("tol", 0.0)
+      gars.check_center_args(mode, param, iters, tol)
+    points = rows + ([start] if start is not None else [])
+    N = len(points)
+    if N > _lib.MAX_ROWS:
+      raise gars.GarInputError(f"cclip: at most {_lib.MAX_ROWS - 1} gradients are supported with a start vector, got {n}")
+    sq = self.global_sqdist(points, total)
+    sub = sq if start is None else sq[:n, :n].contiguous()
+    masks = self.backend.nnm_masks(sub, n, f) if "nnm_masks" in caps else _nnm_masks_torch(sub, n, f)
+    self.last_masks = masks
+    if start is not None:  # the start is point n and mixed row n, alone in its mask
+      own = torch.full((1,), (1 << n) - (1 << 64 if n == 63 else 0), dtype=torch.int64, device=masks.device)
+      masks = torch.cat((masks[:n], own))
+    mixed_leg = self.backend.mixed_sqdist if "mixed_sqdist" in caps else _mixed_sqdist_torch
+    weights_leg = self.backend.mix_weights if "mix_weights" in caps else _mix_weights_torch
+    if rule == "average":
+      even = torch.full((_lib.MAX_ROWS,), 1.0 / n, dtype=torch.float64, device=sq.device)
+      w = weights_leg(masks, N, n, weights=even)
+    else:
+      mixed = mixed_leg(sq, N, masks, N)
+      if rule == "krum":
+        m = args.pop("m", None)
+        if m is None:
+          m = n - f - 2
+        order = self.backend.rank(mixed, n, f, m, _lib.RANK_KRUM)
+        self.last_selection = (order, m)
+        w = weights_leg(masks, N, n, selection=order, m=m)
+      elif rule == "brute":
+        check = args.pop("check", False)
+        if hasattr(self.backend, "brute_select_device"):
+          sel, self.brute_status = self.backend.brute_select_device(mixed, n, f)
+          if check and not (mixed.is_cuda and torch.cuda.is_current_stream_capturing()):
+            code = int(self.brute_status.item())
+            if code == -2:
+              sel = self.backend.index_tensor(self.backend.brute_select(mixed.sqrt().cpu().contiguous(), n, f), rows[0])
+              self.brute_status = None
+            elif code != 0:
+              raise RuntimeError(gars.BRUTE_NO_SUBSET)
+        else:
+          self.brute_status = None
+          sel = self.backend.index_tensor(self.backend.brute_select(mixed.sqrt().cpu().contiguous(), n, f), rows[0])
+        self.last_selection = (sel, n - f)
+        w = weights_leg(masks, N, n, selection=sel, m=n - f)
+      else:
+        cargs = (mixed, n, mode, param, iters, tol, start is not None)
+        cw, info = self.backend.center_weights(*cargs) if "center_weights" in caps else _center_weights_torch(*cargs)
+        self.last_center_info = info
+        w = weights_leg(masks, N, N, weights=cw)
+    self.last_weights = w  # of the ORIGINAL rows (and the start): what the weighted sum reads
+    if "weighted_sum" in caps:
+      return self.backend.weighted_sum(points, w)
+    return _weighted_sum_torch(points, w)
+
+  def nnm(self, local, f, rule="trmean", d_total=None, form="rows", **rule_args):
     """Nearest-neighbour mixing, then `rule` on the mixed rows (gars.nnm), on this rank's slice: (1) the squared
     distances, all-reduced — the neighbours are those of the WHOLE vectors, the same masks on every rank; (2) mixing and
     a coordinate-wise rule are column-local: the fused kernel for median / trmean where the backend has it, else the
     mixed slice is written and the aggregator's own rule runs on it (a distance-based rule then all-reduces the
     distances of the mixed rows).  A backend that declares the "nnm_masks" / "mix_rows" / "colwise_mixed" capabilities
     runs the kernels; any other gets the same steps in plain torch (fp64 ranking, sequential fp32 sums).
-    `self.last_masks` keeps the masks (int64[MAX_ROWS])."""
+    `self.last_masks` keeps the masks (int64[MAX_ROWS]).
+    form="scalars" (krum, brute, geomed, cclip, average; any other rule raises ValueError): `_nnm_scalars` — ONE
+    all-reduce, no mixed row; it also leaves `last_weights` (the weights of the original rows) and, for krum and brute,
+    `last_selection`."""
     from . import gars
     if rule not in self.NNM_RULES:
       raise ValueError(f"nnm: unknown rule {rule!r} ({', '.join(sorted(self.NNM_RULES))})")
+    if form not in ("rows", "scalars"):
+      raise ValueError(f"nnm: unknown form {form!r} (rows, scalars)")
+    if form == "scalars" and rule not in self.SCALAR_RULES:
+      raise ValueError(f"nnm: form='scalars' serves {', '.join(self.SCALAR_RULES)} only, got rule {rule!r}")
     rows = list(local)
     n = len(rows)
     if not 1 <= n <= _lib.MAX_ROWS or not 0 <= f < n:
       raise gars.GarInputError(f"nnm: 1 <= n <= {_lib.MAX_ROWS} and 0 <= f < n are needed, got n = {n}, f = {f}")
     caps = getattr(self.backend, "capabilities", ())
     total = self._total_of(local, d_total)
+    if form == "scalars":
+      return self._nnm_scalars(rows, f, rule, total, rule_args)
     sq = self.global_sqdist(rows, total)
     masks = self.backend.nnm_masks(sq, n, f) if "nnm_masks" in caps else _nnm_masks_torch(sq, n, f)
     self.last_masks = masks

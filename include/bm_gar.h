@@ -617,6 +617,54 @@ int bm_colwise_mixed(int op, const float* const* rows, int n, const uint64_t* ma
                      void* stream);
 int bm_colwise_mixed_max_rows(void);
 
+/* ---------------------------------------------------------------------------------------------
+ * Distance-based rules on mixed rows WITHOUT the mixed rows.  These four entry points joined ABI 23: additions only.
+ *
+ * A mixed row is y_a = (1 / c_a) sum_{i in mask_a} x_i, c_a = popcount(mask_a).  With W_a = mask_a / c_a and
+ * w = W_a - W_b, |y_a - y_b|^2 = -1/2 w' D w, D the squared distances of the ORIGINAL rows; and a weighted sum (or the
+ * mean of a selection) of mixed rows is a weighted sum of the original rows.  So Krum / Multi-Krum, Brute, the
+ * geometric median, centered clipping and the average on mixed rows cost the distance pass, kernels on at most
+ * 64 x 64 scalars and one bm_weighted_sum: no n x d scratch, and one collective when the coordinates are sharded.
+ *
+ * bm_mixed_sqdist: sq = the n_in x n_in fp64 matrix as bm_pairwise_sqdist leaves it (possibly all-reduced); masks =
+ * n_out words as bm_nnm_masks* write them, or one per bucket; out = n_out x n_out fp64, row-major.  The definition,
+ * which fixes the bits (fp64, no contraction):
+ *     D_ij (i != j) is read at (min(i, j), max(i, j)); the diagonal is never read and counts as +0; an entry of D
+ *       outside every pair of masks is never read;
+ *     Q_ib = sum over j in mask_b, j != i, ascending, of D_ij, from +0     (every i < n_in)
+ *     P_ab = sum over i in mask_a, ascending, of Q_ib, from +0
+ *     a != b, named so that mask_a < mask_b AS UNSIGNED 64-BIT WORDS:
+ *       out_ab = P_ab / (c_a c_b) - (1/2) P_aa / c_a^2 - (1/2) P_bb / c_b^2, left to right, a value <= 0 -> +0;
+ *       out_ba = out_ab: bitwise symmetric;  out_aa = +0.  (P_ab and P_ba are one sum in two orders and differ in
+ *       their last bits: the order comes from the masks, not from the indices, so that an entry is a function of the
+ *       two masks alone.  For masks in ascending word order this is "P_ab for a < b".)
+ *     mask_a == mask_b: +0 by an explicit test (the pair reads no distance);
+ *     an empty mask: NaN in its row and column, the diagonal entry included (bm_mix_rows writes a NaN row there);
+ *     P_ab, P_aa or P_bb not finite (any distance read for the pair is not finite): NaN — never clamped to 0.
+ * Rows with equal masks get bitwise-equal rows of out; aliased rows, whose rows of D are bitwise equal, keep their ties.
+ * bm_mixed_sqdist: HOST function on HOST arrays, no stream.  bm_mixed_sqdist_device: the same on DEVICE arrays, one
+ * workgroup, no copy, no synchronisation; the same bits.  Both return BM_EINVAL for a null pointer or n_in / n_out
+ * outside 1 .. BM_MAX_ROWS before any HIP call.  A mask with a bit at or above n_in: BM_EINVAL from the host form;
+ * the device form, which cannot read the masks before it returns, writes NaN to EVERY entry of out. */
+int bm_mixed_sqdist(const double* sq_host, int n_in, const uint64_t* masks_host, int n_out, double* out_host);
+int bm_mixed_sqdist_device(const double* sq_dev, int n_in, const uint64_t* masks_dev, int n_out, double* out_dev,
+                           void* stream);
+
+/* The weights of the ORIGINAL rows behind sum_r w_r y_r.  Exactly one of w_mixed and sel is non-null, else BM_EINVAL:
+ *   w_mixed  fp64[n_out], e.g. what bm_center_weights* leaves;
+ *   sel      int32[m], 1 <= m <= BM_MAX_ROWS: the first m entries of a ranking, or a Brute subset; w_r = the sum, one
+ *            entry at a time in table order from +0, of 1 / m per entry equal to r (duplicates add up).  An entry
+ *            outside 0 .. n_out-1 (-1 after a device Brute search that gave up) makes every w_out[j], j < n_in, NaN,
+ *            as bm_selected_mean answers it.
+ *   w_out[j] = sum over r ascending, w_r != 0 and bit j of mask_r set, of w_r / c_r   (fp64; a NaN w_r counts)
+ * for j < n_in; w_out is fp64[BM_MAX_ROWS] with zeros beyond n_in: what bm_weighted_sum reads.  A mixed row with
+ * w_r != 0 and an empty mask is a NaN row: every w_out[j], j < n_in, is NaN.  Same refusals, same treatment of mask
+ * bits at or above n_in, and the same bits from the host and the device form as above. */
+int bm_mix_weights(const uint64_t* masks_host, int n_in, int n_out, const double* w_mixed, const int32_t* sel, int m,
+                   double* w_out_host);
+int bm_mix_weights_device(const uint64_t* masks_dev, int n_in, int n_out, const double* w_mixed_dev, const int32_t* sel_dev,
+                          int m, double* w_out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
