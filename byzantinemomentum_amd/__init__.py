@@ -10,7 +10,7 @@ from . import stats  # noqa: F401
 from . import layout  # noqa: F401
 from . import graphs  # noqa: F401
 from .gars import (median, trmean, phocas, meamed, krum, bulyan, brute, aksel, average, cge,  # noqa: F401
-                   geomed, cclip, nnm, bucketing)
+                   geomed, cclip, nnm, bucketing, caf, dnc)
 from .stats import (compute_avg_dev_max, anticge_attack, nan_attack, bulyan_attack,  # noqa: F401
                     empire_strict_attack)
 

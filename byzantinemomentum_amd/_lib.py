@@ -45,6 +45,9 @@ ATTACK_EMPIRE, ATTACK_LITTLE, ATTACK_DIRECTION = 0, 1, 16
 CENTER_GEOMED, CENTER_CCLIP = 0, 1  # bm_center_mode
 CENTER_MODES = {"geomed": CENTER_GEOMED, "cclip": CENTER_CCLIP}
 CENTER_MAX_ITERS = 64
+SPECTRAL_CAF, SPECTRAL_DNC = 0, 1  # bm_spectral_mode
+SPECTRAL_MODES = {"caf": SPECTRAL_CAF, "dnc": SPECTRAL_DNC}
+SPECTRAL_MAX_POWER_ITERS = 256
 
 _c_float_pp = ctypes.POINTER(ctypes.c_void_p)
 
@@ -191,6 +194,10 @@ SIGNATURES = {
   "bm_center_weights_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
                                               ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_void_p]),
+  "bm_spectral_weights": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_void_p, ctypes.c_void_p]),
+  "bm_spectral_weights_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
   "bm_weighted_sum": (ctypes.c_int, [_c_float_pp, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                      ctypes.c_void_p]),
   "bm_nnm_masks": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),

@@ -303,6 +303,7 @@ struct Tuning {
   int col_wide;        // BM_COL_WIDE: 1 (default) = median / trimmed mean at 29-52 rows take 16-byte columns, 0 = 8-byte ones (A/B)
   int brute_budget;    // BM_BRUTE_BUDGET: search-tree nodes per wave of the device Brute search before it gives up with status -2 (default 0 = 2^18; tests set a tiny one)
   int wsum_piece;      // BM_WSUM_PIECE: columns per launch piece of bm_weighted_sum (default 0 = 2^29; tests set a small one to walk several pieces)
+  int spectral_lanes;  // BM_SPECTRAL_LANES: lanes per row-dot of bm_spectral_weights*, host and device alike (default 0 = kSpectralLanes of spectral_core.h; 1 = one chain per row: the A/B of profiles/spectral_timings.txt — other bits, the same on both sides)
 };
 const Tuning& tuning();
 Tuning& tuning_mutable();  // bm_tuning_set (A/B runs inside one process)

@@ -14,6 +14,7 @@ Reference semantics, per rule:
 """
 
 import ctypes
+import math
 import weakref
 
 import torch
@@ -25,7 +26,7 @@ __all__ = ["median", "trmean", "phocas", "meamed", "krum", "bulyan", "brute", "a
            "pairwise_sqdist", "rank_from_sqdist", "selected_mean", "bulyan_pass2", "aksel_sqdist",
            "stable_argsort", "GarInputError", "geomed", "cclip", "center_weights", "weighted_sum",
            "nnm", "bucketing", "nnm_masks", "mix_rows", "nnm_rows", "colwise_mixed", "bucket_masks", "NNM_RULES",
-           "mixed_sqdist", "mix_weights", "SCALAR_RULES"]
+           "mixed_sqdist", "mix_weights", "SCALAR_RULES", "caf", "dnc", "spectral_weights"]
 
 
 class GarInputError(ValueError):
@@ -517,6 +518,88 @@ def cclip(gradients, f=None, tau=None, iters=3, tol=0.0, start=None, **kwargs):
 
 
 # ---------------------------------------------------------------------------- #
+# Spectral filtering (CAF, DnC): one distance pass, the filter on scalars, one weighted sum
+
+def check_spectral_args(mode, n, count, power_iters):
+  """The arguments bm_spectral_weights refuses, refused here with their names (a ValueError)."""
+  name = {"caf": "f", "dnc": "k"}.get(mode)
+  if name is None:
+    raise ValueError(f"unknown mode {mode!r} (caf, dnc)")
+  if isinstance(count, bool) or not isinstance(count, int) or count < 0:
+    raise ValueError(f"{mode}: {name} must be an integer >= 0, got {count!r}")
+  if mode == "caf" and not 2 * count < n:
+    raise ValueError(f"caf: 2 f < n is needed, got f = {count} with n = {n}")
+  if mode == "dnc" and not count < n:
+    raise ValueError(f"dnc: k < n is needed, got k = {count} with n = {n}")
+  if (isinstance(power_iters, bool) or not isinstance(power_iters, int)
+      or not 1 <= power_iters <= _lib.SPECTRAL_MAX_POWER_ITERS):
+    raise ValueError(f"{mode}: power_iters must be an integer within 1..{_lib.SPECTRAL_MAX_POWER_ITERS}, "
+                     f"got {power_iters!r}")
+
+
+def spectral_weights(sq, n, mode, count, power_iters=16):
+  """The weights of CAF ("caf", count = f) or DnC ("dnc", count = k rows to remove) from the n x n squared distances of
+  the rows, n <= 64 — the filter of include/bm_gar.h (bm_spectral_weights) on scalars.  `sq` on the device (where
+  pairwise_sqdist left it, possibly all-reduced): one workgroup, no copy, no synchronisation; `sq` on the host: the host
+  form, same bits.  Returns (weights fp64[MAX_ROWS]: the n weights then zeros, info fp64[4]: evaluations run, the lambda
+  of the weights kept, usable rows, the round whose weights were kept or -1), where `sq` lives."""
+  n = int(n)
+  if not 1 <= n <= _lib.MAX_ROWS:
+    raise GarInputError(f"{mode}: at most {_lib.MAX_ROWS} rows are supported, got {n}")
+  check_spectral_args(mode, n, count, power_iters)
+  if sq.dtype != torch.float64 or sq.numel() < n * n or not sq.is_contiguous():
+    raise GarInputError(f"{mode}: expected a contiguous float64 matrix of {n} x {n} squared distances")
+  lib = _lib.load()
+  weights = torch.empty(_lib.MAX_ROWS, dtype=torch.float64, device=sq.device)
+  info = torch.empty(4, dtype=torch.float64, device=sq.device)
+  args = (_ptr(sq), n, _lib.SPECTRAL_MODES[mode], int(count), int(power_iters), _ptr(weights), _ptr(info))
+  if not sq.is_cuda:
+    _lib.check(lib.bm_spectral_weights(*args), "bm_spectral_weights")
+    return weights, info
+  with torch.cuda.device(sq.device):
+    _lib.check(lib.bm_spectral_weights_device(*args, _stream(sq.device)), "bm_spectral_weights_device")
+  return weights, info
+
+
+def _spectral(mode, gradients, count, power_iters):
+  n = len(gradients)
+  if n > _lib.MAX_ROWS:
+    raise GarInputError(f"{mode}: at most {_lib.MAX_ROWS} gradients are supported, got {n}")
+  check_spectral_args(mode, n, count, power_iters)
+  _validate(gradients)
+  weights, info = spectral_weights(pairwise_sqdist(gradients), n, mode, count, power_iters)
+  out = weighted_sum(gradients, weights)
+  out.spectral_weights, out.spectral_info = weights, info
+  return out
+
+
+def caf(gradients, f, power_iters=16, **kwargs):
+  """CAF, the covariance-bound agnostic filter (Allouah, Guerraoui, Gupta, Rizk, Stephan, NeurIPS 2023): while the
+  weights c sum to more than n - 2f, the rows are reweighted c_i <- c_i (1 - tau_i / tau_max), tau_i the squared
+  projection of row i (centred on the weighted mean) on the top eigen-direction of the weighted covariance; the output
+  is the weighted mean under the weights whose top eigenvalue was smallest.  The eigen-direction comes from
+  `power_iters` power steps from the farthest row, a fixed count.  One distance pass, the whole filter on the n x n
+  distances (bm_spectral_weights_device), one weighted sum — whatever the rounds; no host synchronisation.  2 f < n <= 64.
+  The result carries `.spectral_weights` and `.spectral_info` (device tensors)."""
+  return _spectral("caf", gradients, f, power_iters)
+
+
+def dnc(gradients, f, c=1.0, power_iters=16, **kwargs):
+  """DnC, the spectral outlier removal of Shejwalkar & Houmansadr (NDSS 2021) WITHOUT its coordinate sub-sampling and
+  its repeated draws (every coordinate is used, once): the k = min(ceil(c f), n - 1) rows of largest squared projection
+  on the top eigen-direction of the rows' covariance are removed, the output is the mean of the others.  One distance
+  pass, the projections on the n x n distances, one weighted sum; no host synchronisation.  n <= 64.  The result carries
+  `.spectral_weights` and `.spectral_info` (device tensors)."""
+  n = len(gradients)
+  if isinstance(f, bool) or not isinstance(f, int) or f < 0:
+    raise ValueError(f"dnc: f must be an integer >= 0, got {f!r}")
+  if isinstance(c, bool) or not isinstance(c, (int, float)) or not (0 <= c < float("inf")):
+    raise ValueError(f"dnc: c must be a finite number >= 0, got {c!r}")
+  k = min(int(math.ceil(c * f)), max(n - 1, 0))
+  return _spectral("dnc", gradients, k, power_iters)
+
+
+# ---------------------------------------------------------------------------- #
 # Nearest-neighbour mixing and bucketing: one distance pass, the masks on the device, one mixing pass (or none: fused)
 
 def _check_masks(masks, count, where):
@@ -594,7 +677,7 @@ def nnm_rows(gradients, f):
 
 # the rules nnm / bucketing can run on the mixed rows, and whether they take f
 NNM_RULES = {"median": False, "trmean": True, "phocas": True, "meamed": True, "krum": True, "bulyan": True, "brute": True,
-             "aksel": True, "cge": True, "average": False, "geomed": False, "cclip": False}
+             "aksel": True, "cge": True, "average": False, "geomed": False, "cclip": False, "caf": True, "dnc": True}
 
 
 def _rule_on(rule, rows, f, rule_args):

@@ -114,7 +114,7 @@ class HipBackend:
     "step_worker", "momentum_stats_colwise", "momentum_stats_sqdist", "stack_stats_colwise", "stack_stats_sqdist",
     "device_search", "attack_ranking_device", "bulyan_pass2_eval", "order_pair", "colwise_eval", "sqdist2", "anticge",
     "accept_count", "attack_vector", "center_weights", "weighted_sum", "nnm_masks", "mix_rows", "colwise_mixed",
-    "mixed_sqdist", "mix_weights"))
+    "mixed_sqdist", "mix_weights", "spectral_weights"))
 
   def __init__(self):
     from . import gars, stats
@@ -156,6 +156,11 @@ class HipBackend:
     """The weights of the geometric median / centered clipping from the (all-reduced) squared distances, where they
     are (bm_center_weights_device: one workgroup, no synchronisation): (weights fp64[MAX_ROWS], info fp64[3])."""
     return self.gars.center_weights(sq, n, mode, param, iters, tol, has_start)
+
+  def spectral_weights(self, sq, n, mode, count, power_iters):
+    """The weights of CAF / DnC from the (all-reduced) squared distances, where they are (bm_spectral_weights_device:
+    one workgroup, no synchronisation): (weights fp64[MAX_ROWS], info fp64[4])."""
+    return self.gars.spectral_weights(sq, n, mode, count, power_iters)
 
   def weighted_sum(self, gradients, weights):
     return self.gars.weighted_sum(gradients, weights)
@@ -392,6 +397,88 @@ def _center_weights_torch(sq, n, mode, param, iters, tol, has_start):
   return weights, torch.tensor([float(done), move2, float(U)], dtype=torch.float64, device=sq.device)
 
 
+def _spectral_weights_torch(sq, n, mode, count, power_iters):
+  """bm_spectral_weights in plain torch (fp64, where `sq` lives) for a backend without the kernel: the filter of
+  include/bm_gar.h on the squared distances — (weights fp64[MAX_ROWS], info fp64[4])."""
+  D = sq.reshape(-1)[:n * n].reshape(n, n).to(torch.float64)
+  weights = torch.zeros(_lib.MAX_ROWS, dtype=torch.float64, device=sq.device)
+  off = ~torch.eye(n, dtype=torch.bool, device=sq.device)
+  bad = (~torch.isfinite(D) & off).sum(dim=1)
+  usable = ~((bad > 0) & (2 * bad >= n - 1))
+  U = int(usable.sum())
+
+  def info(rounds, lam, kept):
+    return torch.tensor([float(rounds), lam, float(U), float(kept)], dtype=torch.float64, device=sq.device)
+
+  if U == 0:
+    weights[:n] = math.nan
+    return weights, info(0, math.inf, -1)
+  Dz = torch.where(usable[:, None] & usable[None, :], D, torch.zeros_like(D))  # (rows without weight take no part)
+
+  def evaluate(c):  # (tau, lambda) of E(c), None when degenerate
+    C = c.sum()
+    live = c > 0
+    r = torch.where(live, (Dz @ c) / C, torch.zeros_like(c))
+    s = (c * r).sum() / C
+    key = torch.where(live, c * (r - 0.5 * s), torch.zeros_like(c)).clamp_min(0.0)
+    top = key.max()
+    if not float(top) > 0:
+      return None
+    first = int((key == top).nonzero()[0])
+    sc = c.sqrt()
+    z = torch.zeros_like(c)
+    z[first] = sc[first]
+
+    def kz(z):
+      Z = z.sum()
+      return torch.where(live, -0.5 * (Dz @ z - r * Z - (r * z).sum() + s * Z), torch.zeros_like(c))
+
+    for _ in range(power_iters):
+      w = sc * kz(z) / C
+      norm = float((w * w).sum().sqrt())
+      if not (0 < norm < math.inf):
+        break
+      z = sc * (w / norm)
+    q = kz(z)
+    zq = float((z * q).sum())
+    if not zq > 0:
+      return None
+    tau = torch.where(live, q * q, torch.zeros_like(q))
+    return torch.where(torch.isnan(tau), torch.full_like(tau, math.inf), tau), float((c * q * q).sum() / (C * zq))
+
+  c = usable.to(torch.float64)
+  best, lam_best, kept, rounds = c / U, math.inf, -1, 0
+  if mode == "caf":
+    for rnd in range(n):
+      C = float(c.sum())
+      if not C > n - 2 * count:
+        break
+      ev = evaluate(c)
+      if ev is None:
+        break
+      tau, lam = ev
+      rounds = rnd + 1
+      if lam < lam_best:
+        best, lam_best, kept = c / C, lam, rnd
+      tmax = float(tau.max())
+      if not tmax > 0:
+        break
+      ratio = torch.where(tau == tmax, torch.ones_like(tau), tau / tmax)
+      c = torch.where(c > 0, c * (1.0 - ratio), torch.zeros_like(c))
+  else:
+    ev = evaluate(c)
+    tau = torch.zeros_like(c)
+    if ev is not None:
+      tau, lam_best, kept, rounds = ev[0], ev[1], 0, 1
+    drop = max(0, count - (n - U))
+    idx = torch.arange(n, device=sq.device)
+    ahead = usable[None, :] & ((tau[None, :] > tau[:, None]) | ((tau[None, :] == tau[:, None]) & (idx[None, :] > idx[:, None])))
+    keep = usable & (ahead.sum(dim=1) >= drop)
+    best = keep.to(torch.float64) / (U - drop)
+  weights[:n] = best
+  return weights, info(rounds, lam_best, kept)
+
+
 def _weighted_sum_torch(points, weights):
   """bm_weighted_sum in plain torch, accumulated in fp64: rows that are one tensor once, with their weights added; rows
   of weight 0 are not read; a NaN weight gives NaN everywhere."""
@@ -550,6 +637,7 @@ class ShardedAggregator:
     # info (iterations run, move^2, usable rows)
     self.last_weights = None
     self.last_center_info = None
+    self.last_spectral_info = None  # the same for the latest caf / dnc: fp64[4], bm_spectral_weights' info
     self.last_masks = None   # the neighbour masks of the latest nnm of THIS aggregator (int64[MAX_ROWS])
     self._total = None       # (length of the whole vectors, this rank's shard length when it was determined)
 
@@ -847,8 +935,42 @@ class ShardedAggregator:
       raise ValueError("cclip: tau (the clipping radius) is required")
     return self._center("cclip", local, tau, iters, tol, start, d_total)
 
+  def _spectral(self, mode, local, count, power_iters, d_total):
+    """CAF / DnC of the local slice, as `_center`: (1) the squared distances of the rows, all-reduced — the one
+    collective; (2) the weights of the filter, every rank from the same matrix: the same bits; (3) the weighted sum of
+    the local slice.  A backend that declares the "spectral_weights" / "weighted_sum" capabilities runs (2) / (3) as
+    kernels; any other gets the same steps in plain torch, in fp64."""
+    from . import gars
+    rows = list(local)
+    if not rows or len(rows) > _lib.MAX_ROWS:
+      raise gars.GarInputError(f"{mode}: 1..{_lib.MAX_ROWS} gradients are supported, got {len(rows)}")
+    gars.check_spectral_args(mode, len(rows), count, power_iters)
+    caps = getattr(self.backend, "capabilities", ())
+    sq = self.global_sqdist(rows, self._total_of(local, d_total))
+    args = (sq, len(rows), mode, count, power_iters)
+    weights, info = (self.backend.spectral_weights(*args) if "spectral_weights" in caps
+                     else _spectral_weights_torch(*args))
+    self.last_weights, self.last_spectral_info = weights, info
+    if "weighted_sum" in caps:
+      return self.backend.weighted_sum(rows, weights)
+    return _weighted_sum_torch(rows, weights)
+
+  def caf(self, local, f, power_iters=16, d_total=None):
+    """CAF (gars.caf) on this rank's slice.  `self.last_weights` keeps the weights (fp64[MAX_ROWS]: the n weights, then
+    zeros), `self.last_spectral_info` the four numbers of bm_spectral_weights."""
+    return self._spectral("caf", local, f, power_iters, d_total)
+
+  def dnc(self, local, f, c=1.0, power_iters=16, d_total=None):
+    """DnC (gars.dnc) on this rank's slice: the k = min(ceil(c f), n - 1) rows of largest squared projection removed."""
+    if isinstance(f, bool) or not isinstance(f, int) or f < 0:
+      raise ValueError(f"dnc: f must be an integer >= 0, got {f!r}")
+    if isinstance(c, bool) or not isinstance(c, (int, float)) or not (0 <= c < float("inf")):
+      raise ValueError(f"dnc: c must be a finite number >= 0, got {c!r}")
+    k = min(int(math.ceil(c * f)), max(len(local) - 1, 0))
+    return self._spectral("dnc", local, k, power_iters, d_total)
+
   NNM_RULES = ("median", "trmean", "phocas", "meamed", "krum", "bulyan", "brute", "aksel", "cge", "average", "geomed",
-               "cclip")
+               "cclip", "caf", "dnc")
 
   SCALAR_RULES = ("krum", "brute", "geomed", "cclip", "average")
 
@@ -962,7 +1084,7 @@ class ShardedAggregator:
     fn = getattr(self, rule)
     if rule in ("median", "average"):
       return fn(mixed, **rule_args)
-    if rule in ("krum", "bulyan", "brute", "geomed", "cclip"):
+    if rule in ("krum", "bulyan", "brute", "geomed", "cclip", "caf", "dnc"):
       rule_args.setdefault("d_total", total)
     return fn(mixed, f, **rule_args)
 

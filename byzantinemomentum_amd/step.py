@@ -54,8 +54,10 @@ from . import _lib, linesearch
 
 __all__ = ["AggregationStep"]
 
-_RULES = ("krum", "bulyan", "median", "trmean", "phocas", "meamed", "aksel", "brute", "average", "cge", "geomed", "cclip")
+_RULES = ("krum", "bulyan", "median", "trmean", "phocas", "meamed", "aksel", "brute", "average", "cge", "geomed", "cclip",
+          "caf", "dnc")
 _CENTER = {"geomed": ("nu", "iters", "tol"), "cclip": ("tau", "iters", "tol")}  # rule -> the `gar_args` it takes
+_SPECTRAL = {"caf": ("power_iters",), "dnc": ("power_iters", "c")}               # the same for the spectral filters
 _COLWISE = ("median", "trmean", "phocas", "meamed")
 _DISTANCE = ("krum", "bulyan")
 MAX_PAST = 4096  # past sampled averages kept for the curvature term (each is one d-vector of device memory)
@@ -165,7 +167,9 @@ class AggregationStep:
     gar: a rule of the reference, or "geomed" (gar_args nu / iters / tol) / "cclip" (gar_args tau — required — / iters /
     tol): one distance pass, the iteration on scalars, one weighted sum (ShardedAggregator.geomed / .cclip); plain first
     pass, the generic factor search, no acceptation ratio, never the single call.  Centered clipping starts from the
-    previous step's defense vector (`cclip_start`; the mean of the rows on the first step).
+    previous step's defense vector (`cclip_start`; the mean of the rows on the first step).  "caf" (gar_args power_iters)
+    / "dnc" (gar_args power_iters / c), the spectral filters (ShardedAggregator.caf / .dnc), are handled exactly like
+    geomed: f is nb_decl_byz.
     attack: "empire" / "little" (attacks/identical.py), or "anticge" (attacks/anticge.py: no factor — `attack_factor` is
     ignored, `attack_evals` must be None, and 1 <= nb_decl_byz <= honest workers); it runs as its own short chain behind
     the plain first pass (ShardedAggregator.anticge), with every momentum placement, clipping and rule.
@@ -196,6 +200,17 @@ class AggregationStep:
       if gar == "cclip" and "tau" not in args:
         raise ValueError("cclip: gar_args must hold tau (the clipping radius)")
       gars.check_center_args(gar, args.get(radius, 1e-6), args.get("iters", 1), args.get("tol", 0.0))
+    if gar in _SPECTRAL:
+      # caf: power_iters; dnc: power_iters / c — checked here like geomed's, with the row count the rule will see
+      from . import gars
+      args, n = dict(gar_args or {}), nb_workers
+      if set(args) - set(_SPECTRAL[gar]):
+        raise ValueError(f"gar_args of {gar} holds {_SPECTRAL[gar]} and nothing else, got {sorted(args)}")
+      c = args.get("c", 1.0)
+      if isinstance(c, bool) or not isinstance(c, (int, float)) or not (0 <= c < float("inf")):
+        raise ValueError(f"dnc: c must be a finite number >= 0, got {c!r}")
+      count = nb_decl_byz if gar == "caf" else min(int(math.ceil(c * nb_decl_byz)), max(n - 1, 0))
+      gars.check_spectral_args(gar, n, count, args.get("power_iters", 16))
     if momentum_at not in ("worker", "server", "update"):
       raise ValueError(f"momentum_at must be 'worker', 'server' or 'update', got {momentum_at!r}")
     if attack not in _ATTACKS:

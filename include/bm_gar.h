@@ -576,6 +576,41 @@ int bm_center_weights(const double* sq_host, int n, int has_start, int mode, dou
 int bm_center_weights_device(const double* sq_dev, int n, int has_start, int mode, double param, int iters, double tol,
                              double* weights_out_dev, double* info_out_dev, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The spectral filtering rules CAF (covariance-bound agnostic filter: Allouah, Guerraoui, Gupta, Rizk, Stephan, NeurIPS
+ * 2023) and DnC (Shejwalkar & Houmansadr, NDSS 2021, without its coordinate sub-sampling and repeated draws) from ONE
+ * distance pass.  These two entry points joined ABI 23: additions only, no signature changed.  Not in the reference.
+ *
+ * With weights c >= 0 on the rows x_i (C = sum c), mu = sum c_i x_i / C, y_i = x_i - mu and D the n x n squared distances
+ * (bm_pairwise_sqdist), r_i = sum_k c_k D_ik / C and s = sum_i c_i r_i / C give
+ *     <y_i, y_j> = K_ij = -1/2 (D_ij - r_i - r_j + s),   |y_i|^2 = r_i - s / 2,
+ * so the top eigen-direction of the weighted covariance, every projection on it and every reweighting are computed on
+ * scalars (csrc/spectral_core.h, one definition for host and device), and the rule costs one distance pass plus one
+ * bm_weighted_sum whatever the number of rounds or power steps.
+ *   usable      the predicate of bm_center_weights; unusable rows have weight 0 throughout; U = the usable rows; U = 0:
+ *               every weight is NaN.
+ *   evaluation  E(c), c = 0 on the rows without weight, which take no part: start v = y_j, j = argmax c_i |y_i|^2 (ties
+ *               to the lowest index; a maximum that is not > 0: DEGENERATE); power_iters times w = (1/C) sum c_i <y_i, v>
+ *               y_i, v <- w / |w| (a w of no length stops the steps); g_i = <y_i, v / |v|>, tau_i = g_i^2,
+ *               lambda = (1/C) sum c_i g_i^2.  power_iters (1 .. 256) is a fixed count: no convergence test.
+ *   BM_SPECTRAL_CAF (count = f, 0 <= 2 f < n): c = 1 on the usable rows, best = c / U, best lambda = +inf; while
+ *               sum c > n - 2 f, at most n rounds: E(c), stop if degenerate; lambda < best lambda (strictly): best = c / C;
+ *               tau_max = max tau over the rows of weight, stop unless > 0; c_i <- c_i (1 - tau_i / tau_max) — the row of
+ *               largest tau gets exactly 0.  The weights are `best`.
+ *   BM_SPECTRAL_DNC (count = k, 0 <= k < n): one E(c) on c = 1 over the usable rows (degenerate: every tau = 0); the
+ *               k' = max(0, k - (n - U)) usable rows of largest tau are removed, the higher index first among equal tau;
+ *               1 / (U - k') on every other usable row.
+ * weights_out: BM_MAX_ROWS doubles, the n weights (sum 1), then zeros.  info_out: 4 doubles = { evaluations that were
+ * not degenerate, the lambda of the weights kept (+inf: none), U, the 0-based round whose weights were kept (-1: none) }.
+ * bm_spectral_weights: HOST function on a HOST matrix, no stream.  bm_spectral_weights_device: the same on the DEVICE
+ * matrix where bm_pairwise_sqdist left it, one workgroup, no copy, no synchronisation; the same bits as the host form.
+ * Both return BM_EINVAL for a null pointer or a bad n, mode, count or power_iters before any HIP call. */
+enum bm_spectral_mode { BM_SPECTRAL_CAF = 0, BM_SPECTRAL_DNC = 1 };
+int bm_spectral_weights(const double* sq_host, int n, int mode, int count, int power_iters, double* weights_out,
+                        double* info_out);
+int bm_spectral_weights_device(const double* sq_dev, int n, int mode, int count, int power_iters,
+                               double* weights_out_dev, double* info_out_dev, void* stream);
+
 /* out[j] = sum_i w_i rows[i][j] with w_i = (float)weights[i] (weights: DEVICE, n doubles, e.g. where
  * bm_center_weights_device left them): acc = 0, then acc = fmaf(w_i, rows[i][j], acc) over the ACTIVE rows in index order.
  * Rows that are the same pointer form one group: their fp64 weights are added in index order, rounded to fp32 once, and

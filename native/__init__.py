@@ -172,6 +172,26 @@ def register_center_rules():
   return ["native-geomed", "native-cclip"]
 
 
+_spectral_registered = False
+
+
+def register_spectral_rules():
+  """Register `native-caf` and `native-dnc` with the reference's registry: the spectral filtering rules
+  (byzantinemomentum_amd.gars.caf / .dnc; `--gar native-caf`, `--gar native-dnc --gar-args c:1.5`).  NOT done at import,
+  like register_center_rules(): the generic validator, no `influence` (CAF's weights are not a selection).  Returns the
+  names registered."""
+  global _spectral_registered
+  agg = sys.modules.get("aggregators")
+  register = getattr(agg, "register", None)
+  if register is None or not hasattr(agg, "gars"):
+    raise RuntimeError("native.register_spectral_rules() needs the reference's `aggregators` package imported first")
+  if not _spectral_registered:
+    _spectral_registered = True
+    register("native-caf", _gars.caf, _generic_check())
+    register("native-dnc", _gars.dnc, _generic_check())
+  return ["native-caf", "native-dnc"]
+
+
 _nnm_registered = False
 
 
