@@ -12,6 +12,6 @@ from . import graphs  # noqa: F401
 from .gars import (median, trmean, phocas, meamed, krum, bulyan, brute, aksel, average, cge,  # noqa: F401
                    geomed, cclip, nnm, bucketing, caf, dnc)
 from .stats import (compute_avg_dev_max, anticge_attack, nan_attack, bulyan_attack,  # noqa: F401
-                    empire_strict_attack)
+                    empire_strict_attack, minmax_attack, minsum_attack)
 
 __version__ = "0.1.0"

@@ -48,6 +48,11 @@ CENTER_MAX_ITERS = 64
 SPECTRAL_CAF, SPECTRAL_DNC = 0, 1  # bm_spectral_mode
 SPECTRAL_MODES = {"caf": SPECTRAL_CAF, "dnc": SPECTRAL_DNC}
 SPECTRAL_MAX_POWER_ITERS = 256
+PERTURB_SLOTS = MAX_ROWS + 2  # bm_perturb_stats: b_0 .. b_63 | P | N
+PERTURB_P, PERTURB_N = MAX_ROWS, MAX_ROWS + 1
+PERTURB_KINDS = {"unit": 0, "std": 1, "sign": 2}  # bm_perturb_kind
+MINMAX_MODES = {"minmax": 0, "minsum": 1}         # bm_minmax_mode
+MINMAX_OUT = 6  # gamma, bound, binding row, P, N, degenerate
 
 _c_float_pp = ctypes.POINTER(ctypes.c_void_p)
 
@@ -214,6 +219,12 @@ SIGNATURES = {
                                     ctypes.c_int, ctypes.c_void_p]),
   "bm_mix_weights_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                            ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+  "bm_perturb_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64]),
+  "bm_perturb_stats": (ctypes.c_int, [_c_float_pp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+  "bm_minmax_factor": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+  "bm_minmax_factor_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 class Search(ctypes.Structure):

@@ -24,7 +24,8 @@ Tuning& tuning_mutable() {
                            env_int("BM_STUDY_BURST", 8), env_int("BM_STEP_STAGGER_US", 0),
                            env_int("BM_GRAM_STEADY", 1), env_int("BM_BULYAN_SHORT", 1),
                            env_int("BM_PAIR_LOAD_NT", 1), env_int("BM_RANK_ALGO", 0), env_int("BM_COL_WIDE", 1), env_int("BM_BRUTE_BUDGET", 0),
-                           env_int("BM_WSUM_PIECE", 0), env_int("BM_SPECTRAL_LANES", 0)};
+                           env_int("BM_WSUM_PIECE", 0), env_int("BM_SPECTRAL_LANES", 0),
+                           env_int("BM_PERTURB_GRID", 0)};
   return t;
 }
 const Tuning& tuning() { return tuning_mutable(); }
@@ -45,7 +46,8 @@ extern "C" int bm_tuning_set(const char* name, int value) {
       {"BM_STEP_STAGGER_US", &t.step_stagger_us}, {"BM_GRAM_STEADY", &t.gram_steady},
       {"BM_BULYAN_SHORT", &t.bulyan_short}, {"BM_PAIR_LOAD_NT", &t.pair_load_nt},
       {"BM_RANK_ALGO", &t.rank_algo}, {"BM_COL_WIDE", &t.col_wide}, {"BM_BRUTE_BUDGET", &t.brute_budget},
-      {"BM_WSUM_PIECE", &t.wsum_piece}, {"BM_SPECTRAL_LANES", &t.spectral_lanes}};
+      {"BM_WSUM_PIECE", &t.wsum_piece}, {"BM_SPECTRAL_LANES", &t.spectral_lanes},
+      {"BM_PERTURB_GRID", &t.perturb_grid}};
   for (const auto& k : knobs)
     if (strcmp(name, k.key) == 0) {
       *k.slot = value;

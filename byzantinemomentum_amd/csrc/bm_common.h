@@ -304,6 +304,7 @@ struct Tuning {
   int brute_budget;    // BM_BRUTE_BUDGET: search-tree nodes per wave of the device Brute search before it gives up with status -2 (default 0 = 2^18; tests set a tiny one)
   int wsum_piece;      // BM_WSUM_PIECE: columns per launch piece of bm_weighted_sum (default 0 = 2^29; tests set a small one to walk several pieces)
   int spectral_lanes;  // BM_SPECTRAL_LANES: lanes per row-dot of bm_spectral_weights*, host and device alike (default 0 = kSpectralLanes of spectral_core.h; 1 = one chain per row: the A/B of profiles/spectral_timings.txt — other bits, the same on both sides)
+  int perturb_grid;    // BM_PERTURB_GRID: most workgroups of a bm_perturb_stats launch (default 0 = 2047; tests set a tiny one, so that a lane runs past the fp32 -> fp64 fold interval at a small d)
 };
 const Tuning& tuning();
 Tuning& tuning_mutable();  // bm_tuning_set (A/B runs inside one process)

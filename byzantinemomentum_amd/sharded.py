@@ -114,7 +114,7 @@ class HipBackend:
     "step_worker", "momentum_stats_colwise", "momentum_stats_sqdist", "stack_stats_colwise", "stack_stats_sqdist",
     "device_search", "attack_ranking_device", "bulyan_pass2_eval", "order_pair", "colwise_eval", "sqdist2", "anticge",
     "accept_count", "attack_vector", "center_weights", "weighted_sum", "nnm_masks", "mix_rows", "colwise_mixed",
-    "mixed_sqdist", "mix_weights", "spectral_weights"))
+    "mixed_sqdist", "mix_weights", "spectral_weights", "perturb_stats", "minmax_factor"))
 
   def __init__(self):
     from . import gars, stats
@@ -276,6 +276,16 @@ class HipBackend:
   def attack_vector(self, kind, h_avg, factor=None, target=None, want_direction=False):
     return self.stats.attack_vector(kind, h_avg, factor, target, want_direction)
 
+  def perturb_stats(self, honests, perturbation):
+    """(avg, dir, scal) of the Min-Max / Min-Sum attacks on this device's slice of the honest gradients
+    (stats.perturb_stats, bm_perturb_stats): one pass over the rows, no synchronisation."""
+    return self.stats.perturb_stats(honests, perturbation)
+
+  def minmax_factor(self, sq, scal, h, mode):
+    """The closed-form factor from the (all-reduced) distances and scalars, where they are (bm_minmax_factor_device:
+    one workgroup, no synchronisation): fp64[6]."""
+    return self.stats.minmax_factor(sq, scal, h, mode)
+
   def colwise_eval_supported(self, rule, n):
     return self.stats.colwise_eval_supported(rule, n)
 
@@ -327,6 +337,68 @@ def _anticge_scale_torch(vec, scal):
   if attnorm > 0:
     vec.mul_(-math.nextafter(byznorm, 0) / attnorm)
   return vec
+
+
+def _perturb_stats_torch(backend, local, perturbation):
+  """bm_perturb_stats in plain torch for a backend without the kernel: the backend's sequential fp32 average, the
+  direction in fp32, the scalars as fp64 sums of the fp32 vectors."""
+  h = len(local)
+  avg = backend.stack_stats(local)[0]
+  if perturbation == "unit":
+    direction = avg.neg()
+  elif perturbation == "std":
+    direction = torch.stack(list(local)).var(dim=0).sqrt_().neg_() if avg.numel() else avg.clone()
+  else:
+    direction = torch.sign(avg).neg_()
+  p64, a64 = direction.double(), avg.double()
+  scal = torch.zeros(_lib.PERTURB_SLOTS, dtype=torch.float64, device=avg.device)
+  for i in range(h):
+    scal[i] = torch.dot(p64, a64 - local[i].double())
+  scal[_lib.PERTURB_P], scal[_lib.PERTURB_N] = torch.dot(p64, p64), torch.dot(a64, a64)
+  return avg, direction, scal
+
+
+def _minmax_factor_torch(sq, scal, h, mode):
+  """bm_minmax_factor in Python floats (fp64, plain index order: the host form's arithmetic): fp64[6]."""
+  D = sq.reshape(-1)[:h * h].reshape(h, h).tolist()
+  sc = scal.tolist()
+  b, P, N = sc[:h], sc[_lib.PERTURB_P], sc[_lib.PERTURB_N]
+  rowsum = []
+  for i in range(h):
+    t = 0.0
+    for j in range(h):
+      t = t + D[i][j]
+    rowsum.append(t)
+  total = 0.0
+  for t in rowsum:
+    total = total + t
+  a = [max(rowsum[i] / h - total / (2.0 * h * h), 0.0) if not math.isnan(rowsum[i]) else math.nan for i in range(h)]
+  gamma, binding, ok = 0.0, -1.0, P > 0.0 and math.isfinite(P)
+  if mode == "minmax":
+    pairs = [D[i][j] for i in range(h) for j in range(i + 1, h)]
+    bound = math.nan if any(math.isnan(v) for v in pairs) else max(pairs)
+    ok = ok and math.isfinite(bound) and all(math.isfinite(v) for v in a + b)
+    if ok:
+      disc = [b[i] * b[i] + P * (bound - a[i]) for i in range(h)]
+      ok = all(v >= 0.0 for v in disc)
+    if ok:
+      cands = [(-b[i] + math.sqrt(disc[i])) / P for i in range(h)]
+      best = min(range(h), key=lambda i: (cands[i], i))
+      ok = math.isfinite(cands[best])
+      if ok:
+        gamma, binding = cands[best], float(best)
+  else:
+    bound = math.nan if any(math.isnan(v) for v in rowsum) else max(rowsum)
+    A = B = 0.0
+    for i in range(h):
+      A, B = A + a[i], B + b[i]
+    disc = B * B + h * P * (bound - A)
+    ok = ok and math.isfinite(bound) and math.isfinite(A) and math.isfinite(B) and disc >= 0.0
+    if ok:
+      g = (-B + math.sqrt(disc)) / (h * P)
+      ok = math.isfinite(g)
+      gamma = g if ok else 0.0
+  return torch.tensor([gamma, bound, binding, P, N, 0.0 if ok else 1.0], dtype=torch.float64, device=sq.device)
 
 
 def _attack_vector_torch(kind, avg, factor, target, want_direction):
@@ -1107,6 +1179,45 @@ class ShardedAggregator:
     byz, _, scal = _anticge_sum_torch(self.backend, local, f_decl, self._all_reduce(self.backend.row_sqnorms(local)))
     self._all_reduce(scal[:1])
     return [_anticge_scale_torch(byz, scal)] * f_real
+
+  def minmax(self, local_honests, f_real, mode="minmax", perturbation="std", d_total=None):
+    """The Min-Max ("minmax") / Min-Sum ("minsum") attack of Shejwalkar & Houmansadr (NDSS 2021) on this rank's slice of
+    the honest gradients (stats.minmax_attack): `f_real` references to ONE new vector avg + gamma * p.  The h x h squared
+    distances and the scalars of the perturbation are both sums over coordinates: they travel through ONE all-reduce,
+    h^2 + PERTURB_SLOTS doubles, concatenated — none with one rank, never a d-sized one — and every rank forms gamma
+    from the same numbers: the same bits.  A backend that declares the "perturb_stats" / "minmax_factor" capabilities
+    runs those legs as kernels and leaves gamma on the device; any other gets plain-torch fp64 legs.  The vector
+    carries `.attack_factor` (fp64[1]) and `.attack_info` (fp64[6], bm_minmax_factor's)."""
+    if mode not in _lib.MINMAX_MODES:
+      raise ValueError(f"unknown mode {mode!r} (one of {sorted(_lib.MINMAX_MODES)})")
+    if perturbation not in _lib.PERTURB_KINDS:
+      raise ValueError(f"unknown perturbation {perturbation!r} (one of {sorted(_lib.PERTURB_KINDS)})")
+    local = list(local_honests)
+    h = len(local)
+    if not 2 <= h <= _lib.MAX_ROWS:
+      raise ValueError(f"the {mode} attack needs 2 <= h <= {_lib.MAX_ROWS} honest gradients, got h = {h}")
+    if f_real <= 0:
+      return []
+    caps = getattr(self.backend, "capabilities", ())
+    if "perturb_stats" in caps:
+      avg, direction, scal = self.backend.perturb_stats(local, perturbation)
+    else:
+      avg, direction, scal = _perturb_stats_torch(self.backend, local, perturbation)
+    sq = self.backend.pairwise_sqdist(local, d_total=self._total_of(local_honests, d_total))
+    if self.collective:
+      both = torch.cat([sq.reshape(-1), scal])
+      self._all_reduce(both)
+      sq, scal = both[:h * h].view(h, h), both[h * h:]
+    if "minmax_factor" in caps:
+      info = self.backend.minmax_factor(sq, scal, h, mode)
+      factor = info  # (read by the kernel where it is)
+    else:
+      info = _minmax_factor_torch(sq, scal, h, mode)
+      factor = info[0].item()
+    byz = torch.empty_like(avg)
+    self.backend.multi_fma3([byz], [avg], [direction], 1.0, factor)
+    byz.attack_factor, byz.attack_info = info[:1], info
+    return [byz] * f_real
 
   def attack_vector(self, kind, local_avg, factor=None, target_idx=None, d_total=None, want_direction=False):
     """This rank's slice of the Byzantine vector of the `nan` / `bulyan` / `empire-strict` attacks from its slice of

@@ -18,7 +18,8 @@ from . import gars
 __all__ = ["compute_avg_dev_max", "stack_stats_async", "study_dots", "study_stats", "multi_axpby", "row_sqnorms", "momentum_stats", "momentum_stats_colwise", "momentum_stats_sqdist", "stack_stats_colwise", "stack_stats_sqdist",
            "multi_fma3", "clip_factors", "clip_factors_from_sq", "multi_scale", "clip_gradients", "l2_distance",
            "step_worker", "anticge_sum", "anticge_scale", "anticge_attack", "accept_count",
-           "attack_vector", "nan_attack", "bulyan_attack", "empire_strict_attack"]
+           "attack_vector", "nan_attack", "bulyan_attack", "empire_strict_attack",
+           "perturb_stats", "minmax_factor", "minmax_attack", "minsum_attack"]
 
 _ptr = gars._ptr
 
@@ -329,6 +330,102 @@ def anticge_attack(grad_honests, f_decl, f_real, **kwargs):
     return [torch.full_like(grad_honests[0], math.nan)] * f_real
   byz, _, scal = anticge_sum(grad_honests, f_decl, row_sqnorms(grad_honests).contiguous())
   return [anticge_scale(byz, scal)] * f_real
+
+
+def _perturbation_id(perturbation):
+  if perturbation not in _lib.PERTURB_KINDS:
+    raise gars.GarInputError(f"unknown perturbation {perturbation!r} (one of {sorted(_lib.PERTURB_KINDS)})")
+  return _lib.PERTURB_KINDS[perturbation]
+
+
+def _minmax_mode_id(mode):
+  if mode not in _lib.MINMAX_MODES:
+    raise gars.GarInputError(f"unknown mode {mode!r} (one of {sorted(_lib.MINMAX_MODES)})")
+  return _lib.MINMAX_MODES[mode]
+
+
+def _require_honests(h, what):
+  if not 2 <= h <= _lib.MAX_ROWS:
+    raise gars.GarInputError(f"{what} needs 2 <= h <= {_lib.MAX_ROWS} honest gradients, got h = {h}")
+
+
+def perturb_stats(grad_honests, perturbation):
+  """What the closed form of the Min-Max / Min-Sum attacks needs from the vectors, in ONE pass over the h honest rows
+  (bm_perturb_stats, include/bm_gar.h): (avg, dir, scal) — the sequential fp32 average (the bits of stack_stats_async's),
+  the perturbation direction p ("unit": -avg, "std": -sqrt(unbiased column variance), "sign": -sign(avg)) and the
+  device fp64[PERTURB_SLOTS] scalars [b_0 .. b_{h-1}, zeros, |p|^2, |avg|^2], b_i = <p, avg - g_i>, over THESE
+  coordinates (all are sums: under sharding they are all-reduced).  Fresh tensors; no sync."""
+  kind = _perturbation_id(perturbation)
+  grad_honests = list(grad_honests)
+  _require_honests(len(grad_honests), "perturb_stats")
+  h, d, device = gars._validate(grad_honests)
+  lib = _lib.load()
+  avg = torch.empty(d, dtype=torch.float32, device=device)
+  direction = torch.empty(d, dtype=torch.float32, device=device)
+  scal = torch.empty(_lib.PERTURB_SLOTS, dtype=torch.float64, device=device)
+  ws = gars._Scratch.get(device, "ws_perturb", nbytes=int(lib.bm_perturb_workspace_bytes(d)))
+  with torch.cuda.device(device):
+    _lib.check(lib.bm_perturb_stats(_lib.pointer_table(grad_honests), h, d, kind, _ptr(avg), _ptr(direction), _ptr(scal),
+                                    _ptr(ws), gars._stream(device)), "bm_perturb_stats")
+  return avg, direction, scal
+
+
+def minmax_factor(sq, scal, h, mode):
+  """The closed-form factor of the Min-Max ("minmax") or Min-Sum ("minsum") attack (bm_minmax_factor, include/bm_gar.h)
+  from the h x h squared distances of the honest rows and the scalars of perturb_stats — both possibly all-reduced.
+  `sq` on the device: one workgroup, no copy, no synchronisation; `sq` on the host: the host form, same bits.  Returns
+  fp64[6] where `sq` lives: [gamma, the bound R or S, the binding row or -1, |p|^2, |avg|^2, degenerate 0 / 1]."""
+  mode_id = _minmax_mode_id(mode)
+  h = int(h)
+  _require_honests(h, mode)
+  for t, count, what in ((sq, h * h, f"a matrix of {h} x {h} squared distances"),
+                         (scal, _lib.PERTURB_SLOTS, f"the {_lib.PERTURB_SLOTS} scalars of perturb_stats")):
+    if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.numel() >= count and t.is_contiguous()):
+      raise gars.GarInputError(f"{mode}: expected a contiguous float64 tensor holding {what}")
+  if scal.device != sq.device:
+    raise gars.GarInputError(f"{mode}: the distances and the scalars must live on one device")
+  lib = _lib.load()
+  out = torch.empty(_lib.MINMAX_OUT, dtype=torch.float64, device=sq.device)
+  args = (_ptr(sq), _ptr(scal), h, mode_id, _ptr(out))
+  if not sq.is_cuda:
+    _lib.check(lib.bm_minmax_factor(*args), "bm_minmax_factor")
+    return out
+  with torch.cuda.device(sq.device):
+    _lib.check(lib.bm_minmax_factor_device(*args, gars._stream(sq.device)), "bm_minmax_factor_device")
+  return out
+
+
+def _minmax_attack(mode, grad_honests, f_real, perturbation):
+  _perturbation_id(perturbation)
+  grad_honests = list(grad_honests)
+  _require_honests(len(grad_honests), f"the {mode} attack")
+  h = gars._validate(grad_honests)[0]
+  if f_real <= 0:
+    return []
+  avg, direction, scal = perturb_stats(grad_honests, perturbation)
+  info = minmax_factor(gars.pairwise_sqdist(grad_honests), scal, h, mode)
+  byz = torch.empty_like(avg)
+  multi_fma3([byz], [avg], [direction], 1.0, info)  # avg + gamma * p, gamma read where the kernel left it
+  byz.attack_factor, byz.attack_info = info[:1], info
+  return [byz] * f_real
+
+
+def minmax_attack(grad_honests, f_real, perturbation="std", **kwargs):
+  """The Min-Max attack of Shejwalkar & Houmansadr (NDSS 2021), in the shape of the reference's attacks: `f_real`
+  references to ONE new tensor avg + gamma * p, gamma the largest factor that keeps the vector no farther from any
+  honest gradient than the two farthest honest gradients are from each other.  gamma is the closed form of
+  include/bm_gar.h, not the paper's halving search: one pass over the rows for the scalars (perturb_stats), the distance
+  pass, one workgroup on scalars (minmax_factor) and one streaming kernel for the vector, all on the current stream
+  without a synchronisation.  perturbation: "unit", "std" (default) or "sign".  The tensor carries `.attack_factor`
+  (device fp64[1]) and `.attack_info` (device fp64[6], minmax_factor's).  2 <= h <= 64 honest gradients.
+  **kwargs: ignored, like the keyword arguments the reference's attacks are handed and do not know."""
+  return _minmax_attack("minmax", grad_honests, f_real, perturbation)
+
+
+def minsum_attack(grad_honests, f_real, perturbation="std", **kwargs):
+  """The Min-Sum attack of the same paper: as minmax_attack, with gamma the largest factor that keeps the SUM of the
+  vector's squared distances to the honest gradients within the largest such sum of an honest gradient."""
+  return _minmax_attack("minsum", grad_honests, f_real, perturbation)
 
 
 def attack_vector(kind, h_avg, factor=None, target=None, want_direction=False):

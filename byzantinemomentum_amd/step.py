@@ -12,6 +12,9 @@ is one row of the _ATTACK table, what the constructor's arguments decide is the 
                                    |GAR(honests + [avg_h + t*dir]*f) - avg_h|^2         attacks/identical.py:67-77
      or the "anticge" attack       byz = -(sum of the h - f_decl smallest honests), scaled to just below the next norm,
                                    repeated f_real times; no factor                     attacks/anticge.py:49-78
+     or "minmax" / "minsum"        byz = avg_h + gamma*p, gamma the closed form of the Min-Max / Min-Sum attacks
+                                   (Shejwalkar & Houmansadr, NDSS 2021; include/bm_gar.h), p one of three perturbations;
+                                   no factor to give or search                          ShardedAggregator.minmax
      or "nan" / "hidden" / "empire-strict"  byz = all NaN | avg_h + factor*(ones or e_target) | avg_h*(-eps), ONE streaming
                                    kernel behind the plain first pass (bm_attack_vector); "hidden" is the reference's
                                    `bulyan` attack, factor and eps fixed or searched   attacks/nan.py:36-40,
@@ -67,7 +70,7 @@ class _Attack(NamedTuple):
   """What the step needs to know of an attack: one row of _ATTACK per name, read by the constructor, _make_plan, the
   factor search and _byzantine — none of them compares names."""
   formed: str               # who forms the vector: "first_pass" (in its kernel), or behind the PLAIN first pass "chain"
-                            # (ShardedAggregator.anticge) / "kernel" (ShardedAggregator.attack_vector)
+                            # (_CHAIN[first_pass]: ShardedAggregator.anticge / .minmax) / "kernel" (ShardedAggregator.attack_vector)
   kind: Optional[str]       # "kernel": the kind attack_vector is handed ("shift_one": "shift_all" with target_idx "all")
   first_pass: str           # the attack the first pass is handed: what it forms, for empire-strict the direction it forms
                             # for a search (a first pass that forms nothing is handed the name, unread)
@@ -79,17 +82,37 @@ class _Attack(NamedTuple):
   shift: float              # added to every abscissa of a search (avg * (-x) is avg + (1 + x) * (-avg): empire.py:51-59)
   apply: Optional[str]      # the found factor: "fma" = multi_fma3 along the direction (identical.py:82-84), "scale" =
                             # attack_vector("scale", avg, -epsilon), the factor being a positive integer epsilon (empire.py:61-62)
+  needs: Optional[str] = None  # "chain": what it asks of the worker counts — "f_decl" = 1 <= nb_decl_byz <= honest
+                               # workers (anticge.py:67-68), "pair" = at least two honest workers (a distance between two)
 
 
 _ATTACK = {
   "empire": _Attack("first_pass", None, "empire", True, True, frozenset(), "first_pass", 0.0, "fma"),
   "little": _Attack("first_pass", None, "little", True, True, frozenset(), "first_pass", 0.0, "fma"),
-  "anticge": _Attack("chain", None, "anticge", False, True, frozenset(), None, 0.0, None),
+  "anticge": _Attack("chain", None, "anticge", False, True, frozenset(), None, 0.0, None, "f_decl"),
   "nan": _Attack("kernel", "nan", "nan", False, True, frozenset(), None, 0.0, None),
   "hidden": _Attack("kernel", "shift_one", "hidden", True, True, frozenset({"target_idx"}), "kernel", 0.0, "fma"),
   "empire-strict": _Attack("kernel", "scale", "empire", True, False, frozenset(), "first_pass", 1.0, "scale"),
 }
 _ATTACKS = tuple(_ATTACK)
+# The attacks the reference does not ship, in a table of their own (the one above is the reference's, attack for attack):
+# the closed-form Min-Max / Min-Sum attacks, chains like anticge.  The constructor looks a name up in both.
+_ATTACK_BEYOND = {
+  "minmax": _Attack("chain", None, "minmax", False, True, frozenset({"perturbation"}), None, 0.0, None, "pair"),
+  "minsum": _Attack("chain", None, "minsum", False, True, frozenset({"perturbation"}), None, 0.0, None, "pair"),
+}
+_PERTURBATIONS = tuple(_lib.PERTURB_KINDS)
+# "chain": the short sequence behind the plain first pass, by the name the row carries as `first_pass` (the first pass
+# itself forms nothing and does not read it): (step, honest rows) -> the f_real references to the Byzantine vector
+_CHAIN = {
+  "anticge": lambda step, honests: step.agg.anticge(honests, step.f_decl, step.f_real),
+  "minmax": lambda step, honests: step.agg.minmax(honests, step.f_real, "minmax", step.perturbation),
+  "minsum": lambda step, honests: step.agg.minmax(honests, step.f_real, "minsum", step.perturbation),
+}
+
+
+def _attack_row(name):
+  return _ATTACK.get(name) or _ATTACK_BEYOND.get(name)
 
 
 class StepPlan(NamedTuple):
@@ -179,7 +202,13 @@ class AggregationStep:
     "empire-strict" (attacks/empire.py: `attack_factor` is epsilon, a positive int, or `attack_evals` = E its
     `epsilon:-E`; it has no `negative`) are one streaming kernel behind the plain first pass
     (ShardedAggregator.attack_vector); never the single call.
-    attack_args: further arguments of the attack, for "hidden" alone.
+    "minmax" / "minsum" (Shejwalkar & Houmansadr, NDSS 2021, not in the reference): the closed-form factor of
+    include/bm_gar.h on the honest rows the rule is about to see — no factor: `attack_factor` is ignored as for anticge,
+    `attack_evals` must be None; attack_args={"perturbation": "unit" | "std" | "sign"}, default "std"; at least two
+    honest workers.  A chain behind the plain first pass like anticge (ShardedAggregator.minmax): every rule, momentum
+    placement and clipping, never the single call.  `last_factor` is then the DEVICE tensor holding gamma (no read, no
+    synchronisation), `last_byzantine.attack_info` the six numbers of bm_minmax_factor.
+    attack_args: further arguments of the attack, for "hidden" and "minmax" / "minsum" alone.
     attack_evals: None = the fixed `attack_factor`; a positive integer E = the reference's `factor:-E` (its
     default is -16): the factor is searched each step with tools.line_maximize's exploration
     (identical.py:67-77), `attack_negative` being the attack's `negative` argument during the search.
@@ -213,19 +242,29 @@ class AggregationStep:
       gars.check_spectral_args(gar, n, count, args.get("power_iters", 16))
     if momentum_at not in ("worker", "server", "update"):
       raise ValueError(f"momentum_at must be 'worker', 'server' or 'update', got {momentum_at!r}")
-    if attack not in _ATTACKS:
+    if _attack_row(attack) is None:
       hint = "; the reference's `bulyan` attack is \"hidden\" here (bulyan names a rule)" if attack == "bulyan" else ""
       raise ValueError(f"unknown attack {attack!r} (empire, little, hidden: factor, use a negative one for negative:True; "
-                       f"empire-strict: epsilon; anticge, nan: no factor){hint}")
+                       f"empire-strict: epsilon; anticge, nan: no factor){hint}")  # (and minmax, minsum: no factor)
     if attack_evals is not None and (not isinstance(attack_evals, int) or attack_evals < 1):
       raise ValueError(f"attack_evals must be a positive number of evaluations, got {attack_evals!r}")
-    att = _ATTACK[attack]
+    att = _attack_row(attack)
     if not att.factor and attack_evals is not None:
       raise ValueError(f"the {attack} attack has no factor to search: attack_evals must be None")
-    if att.formed == "chain" and nb_real_byz >= 1 and not 1 <= nb_decl_byz <= nb_workers - nb_real_byz:
+    if att.needs == "f_decl" and nb_real_byz >= 1 and not 1 <= nb_decl_byz <= nb_workers - nb_real_byz:
       raise ValueError(f"the anticge attack needs 1 <= nb_decl_byz <= {nb_workers - nb_real_byz} honest workers "
                        f"(attacks/anticge.py:67-68 indexes the sorted norms at h - f_decl), got {nb_decl_byz}")
-    if attack_args is not None and (not att.args or not isinstance(attack_args, dict) or set(attack_args) - att.args):
+    if att.needs == "pair" and nb_real_byz >= 1 and nb_workers - nb_real_byz < 2:
+      raise ValueError(f"the {attack} attack needs at least 2 honest workers (a distance between two of them), got "
+                       f"{nb_workers - nb_real_byz}")
+    if "perturbation" in att.args:
+      if attack_args is not None and (not isinstance(attack_args, dict) or set(attack_args) - att.args):
+        raise ValueError(f"attack_args holds {{'perturbation': {' | '.join(map(repr, _PERTURBATIONS))}}} for the {attack} "
+                         f"attack and nothing else, got {attack_args!r}")
+      if (attack_args or {}).get("perturbation", "std") not in _PERTURBATIONS:
+        raise ValueError(f"perturbation must be one of {', '.join(map(repr, _PERTURBATIONS))}, got "
+                         f"{attack_args['perturbation']!r}")
+    elif attack_args is not None and (not att.args or not isinstance(attack_args, dict) or set(attack_args) - att.args):
       raise ValueError(f"attack_args holds {{'target_idx': int | 'all'}} for the hidden attack and nothing else, "
                        f"got {attack_args!r} with attack {attack!r}")
     target_idx = (attack_args or {}).get("target_idx", -1)
@@ -258,6 +297,7 @@ class AggregationStep:
     self.momentum_at = momentum_at
     self.attack = attack
     self.target_idx = target_idx
+    self.perturbation = (attack_args or {}).get("perturbation", "std") if "perturbation" in att.args else None
     self.factor = attack_factor
     self.clip = gradient_clip
     self.attack_evals = attack_evals
@@ -294,7 +334,7 @@ class AggregationStep:
     analytic = self.line_search in ("auto", "host")
     # the first pass: momentum_stats* (worker placement) and stack_stats* (update placement) make the same choice
     stem = {"worker": "momentum_stats_", "update": "stack_stats_"}.get(self.momentum_at)
-    att = _ATTACK[self.attack]
+    att = _attack_row(self.attack)
     behind = att.formed != "first_pass"
     if not fixed and att.direction == "first_pass":  # (empire-strict: the empire direction, -avg)
       first_pass = "direction"
@@ -336,9 +376,9 @@ class AggregationStep:
   def last_factor(self):
     """The factor of the last step (the searched one with attack_evals).  After a device search this is the read that
     synchronises; a step that never looks costs nothing."""
-    if isinstance(self._factor_now, torch.Tensor):
+    if isinstance(self._factor_now, torch.Tensor) and isinstance(self._search_now, torch.Tensor):
       self._settle_search()
-    return self._factor_now
+    return self._factor_now  # (minmax / minsum: the device tensor the chain left, handed out as it is)
 
   @last_factor.setter
   def last_factor(self, value):
@@ -650,9 +690,12 @@ class AggregationStep:
     honests, h_avg, byz = first.honests, first.h_avg, first.byz
     searched = plan.search is not None
     if att.formed == "chain" and self.f_real > 0:
-      # attacks/anticge.py:49-78 on the honest gradients the rule is about to see (the updated buffers under worker
-      # placement): row norms, ranking, sum and scaling on the device, two small collectives under sharding
-      byz = agg.anticge(honests, self.f_decl, self.f_real)[0]
+      # on the honest gradients the rule is about to see (the updated buffers under worker placement).  anticge
+      # (attacks/anticge.py:49-78): row norms, ranking, sum and scaling on the device, two small collectives under
+      # sharding; minmax / minsum: one pass for the scalars, the distance pass, the closed form, one collective
+      byz = _CHAIN[att.first_pass](self, honests)[0]
+      if hasattr(byz, "attack_factor"):
+        self.last_factor, self.last_search = byz.attack_factor, None
     if att.formed == "kernel" and self.f_real > 0:
       # one streaming kernel on the honest average (bm_attack_vector); with a search, `hidden` takes its 0 / 1 direction
       # from the same kernel at factor 1 and empire-strict waits for its epsilon

@@ -700,6 +700,53 @@ int bm_mix_weights(const uint64_t* masks_host, int n_in, int n_out, const double
 int bm_mix_weights_device(const uint64_t* masks_dev, int n_in, int n_out, const double* w_mixed_dev, const int32_t* sel_dev,
                           int m, double* w_out_dev, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The Min-Max and Min-Sum attacks (Shejwalkar, Houmansadr, "Manipulating the Byzantine", NDSS 2021), closed form.  These
+ * entry points joined ABI 23: additions only, no signature changed.
+ *
+ * Honest rows g_1 .. g_h, 2 <= h <= BM_MAX_ROWS, D_ij = |g_i - g_j|^2 (bm_pairwise_sqdist).  The Byzantine vector is
+ * m = avg + gamma p: avg the sequential fp32 mean bm_stack_stats writes (same bits), p a perturbation direction, gamma
+ * the largest factor that keeps m as close to the honest rows as they are to each other.  Every distance involved is a
+ * quadratic in gamma with scalar coefficients, so gamma has a closed form (the paper halves a step on d-sized vectors).
+ *   p      BM_PERTURB_UNIT  -avg                 (the paper's -avg / |avg| unnormalised: same m, gamma in units of |avg|)
+ *          BM_PERTURB_STD   -sqrt(q / (h - 1))   q = the column's sum (x - avg)^2 as bm_stack_stats forms it: the bits of
+ *                                                its BM_ATTACK_LITTLE | BM_ATTACK_DIRECTION output at scale -1
+ *          BM_PERTURB_SIGN  -sign(avg)           sign(+-0) = 0, a NaN stays NaN
+ *   b_i = <p, avg - g_i>  (sum of p_c (avg_c - g_ic), not a difference of two dots)    P = |p|^2    N = |avg|^2
+ *   a_i = |avg - g_i|^2 = (1/h) sum_j D_ij - (1/(2 h^2)) sum_ij D_ij, from D; a value <= 0 counts as +0
+ *   Min-Max  R = max_{i<j} D_ij;  gamma_i = (-b_i + sqrt(b_i^2 + P (R - a_i))) / P;  gamma = min_i gamma_i, ties to the
+ *            lower index: the binding row
+ *   Min-Sum  S = max_i sum_j D_ij, A = sum_i a_i, B = sum_i b_i (the computed one, analytically 0);
+ *            gamma = (-B + sqrt(B^2 + h P (S - A))) / (h P)
+ *   degenerate: P not > 0, a scalar the formula reads (or gamma) not finite, or a negative discriminant: gamma = +0 and
+ *            the flag is set — the vector is then avg itself.
+ * Every fp64 sum runs in plain index order (the row sums of D over j, the sums over the rows over i), on host and
+ * device alike.
+ *
+ * bm_perturb_stats: ONE pass over the h rows (h + 2 row units of traffic): avg_out and dir_out = p (DEVICE, d floats
+ *   each, must not overlap each other or a row) and scal_out (DEVICE, BM_PERTURB_SLOTS doubles) = { b_0 .. b_{h-1}, zeros
+ *   up to BM_MAX_ROWS, P, N } over the d coordinates given — this shard's part: all are sums over coordinates.  Per-lane
+ *   fp32 chains of at most 16 iterations, then fp64: across the wave, per workgroup into ws
+ *   (bm_perturb_workspace_bytes(d)), and a finish kernel that adds the workgroups' partials in a fixed order.  No float
+ *   atomics, no synchronisation: two calls on the same input give the same bits.  Rows may be separately allocated, of
+ *   any 4-byte alignment.  d == 0 is legal (an empty shard): the scalars are zeros.  BM_EINVAL before any HIP call for a
+ *   null pointer (avg_out / dir_out may be NULL when d == 0), h outside 2 .. BM_MAX_ROWS, an unknown kind, d < 0 or
+ *   overlapping outputs.
+ * bm_minmax_factor: HOST function on HOST arrays (sq: h x h doubles, scal: BM_PERTURB_SLOTS doubles), no stream.
+ *   bm_minmax_factor_device: the same on the DEVICE arrays where bm_pairwise_sqdist and bm_perturb_stats left them, one
+ *   workgroup, D in LDS, no copy, no synchronisation; the same bits (csrc/minmax_core.h, one definition for both).
+ *   out: 6 doubles = { gamma, the bound R or S, the binding row (-1: Min-Sum, or degenerate), P, N, degenerate 0 / 1 }.
+ *   BM_EINVAL for a null pointer, h outside 2 .. BM_MAX_ROWS or an unknown mode before any HIP call.
+ * The vector: bm_multi_fma3_bdev(out, avg, dir, a = 1, b_dev = &out[0]). */
+#define BM_PERTURB_SLOTS (BM_MAX_ROWS + 2)
+enum bm_perturb_kind { BM_PERTURB_UNIT = 0, BM_PERTURB_STD = 1, BM_PERTURB_SIGN = 2 };
+enum bm_minmax_mode { BM_MINMAX = 0, BM_MINSUM = 1 };
+int64_t bm_perturb_workspace_bytes(int64_t d);
+int bm_perturb_stats(const float* const* rows, int h, int64_t d, int kind, float* avg_out, float* dir_out,
+                     double* scal_out, void* ws, void* stream);
+int bm_minmax_factor(const double* sq_host, const double* scal_host, int h, int mode, double* out_host);
+int bm_minmax_factor_device(const double* sq_dev, const double* scal_dev, int h, int mode, double* out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
