@@ -1,8 +1,9 @@
 """The Min-Max / Min-Sum attacks on the GPU (bm_perturb_stats -> distance pass -> bm_minmax_factor_device ->
 bm_multi_fma3_bdev).  Needs an MI355X: `pytest -m gpu`.  Rows are separately allocated tensors.
   (7)  avg_out has the bits of bm_stack_stats' average; dir_out the bits of its LITTLE | DIRECTION output at scale -1
-       ("std"), -avg exactly ("unit"), -sign(avg) exactly ("sign") — at every row-count class (8 rows each) and vector
-       width (rows offset by 0, 1 and 2 floats), lengths with and without a tail;
+       ("std"), -avg exactly ("unit"), -sign(avg) exactly ("sign") — at every row-count class (8 rows each) and at
+       both ends of every class (CLASS_EDGES, which (8) and (9) run as well), every vector width (rows offset by 0, 1
+       and 2 floats), lengths with and without a tail;
   (8)  the scalars against float64 sums of the device's OWN fp32 avg / dir and the rows — only the summation is
        measured —, as |error| / sum |terms|; one case with the grid capped (BM_PERTURB_GRID) at d = 100 003, where a lane
        runs 49-196 iterations (the fp32 -> fp64 fold is reached) and several workgroups contribute;
@@ -29,6 +30,9 @@ pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 HS = (2, 3, 11, 20, 27, 39, 45, 50, 64)   # every row-count class of the dispatch: 8, 8, 16, 24, 32, 40, 48, 56, 64
+# the last row count of a class and the first of the next (has(i) deciding the last 8 rows; from 25 rows on the pointer
+# table travels in the kernel-argument segment): run through (7), (8) and (9); the bars were measured over HS
+CLASS_EDGES = (8, 9, 16, 17, 24, 25, 32, 33, 40, 41, 48, 49, 56, 57)
 DS = (1, 3, 63, 1027, 4100)
 OFFSETS = (0, 1, 2)                       # floats: vector widths 4, 1, 2
 BAR_SCALARS = 3.98e-07
@@ -83,7 +87,7 @@ def scalar_errors(rows, avg, direction, scal):
 # ---------------------------------------------------------------------------- #
 # (7)
 
-@pytest.mark.parametrize("h", HS)
+@pytest.mark.parametrize("h", HS + CLASS_EDGES)
 def test_average_and_direction_bits(bm, h):
   for d in DS:
     for offset in OFFSETS:
@@ -134,7 +138,7 @@ def measure_scalars_capped(bm, h, grid=2, d=100003):
   return worst
 
 
-@pytest.mark.parametrize("h", HS)
+@pytest.mark.parametrize("h", HS + CLASS_EDGES)
 def test_scalars_against_float64_sums_of_the_device_vectors(bm, h):
   worst = measure_scalars(bm, h)
   print(f"h = {h}: scalars, worst |error| / sum |terms| = {worst:.3e} (bar {BAR_SCALARS:.1e})")
@@ -158,7 +162,7 @@ def test_empty_vectors_give_zero_scalars(bm):
 # ---------------------------------------------------------------------------- #
 # (9)
 
-@pytest.mark.parametrize("h", HS)
+@pytest.mark.parametrize("h", HS + CLASS_EDGES)
 def test_same_bits_twice_and_device_factor_equals_host_factor(bm, h):
   for d, offset in ((63, 1), (4100, 0), (1027, 2)):
     rows = device_rows(host_rows(h, d), offset)
