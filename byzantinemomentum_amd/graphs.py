@@ -37,7 +37,11 @@ class GraphCaptureError(RuntimeError):
 
 
 class GraphedCall:
-  """`fn()` (any call of this package whose tensors live on the current GPU) recorded into a HIP graph."""
+  """`fn()` (any call of this package whose tensors live on the current GPU) recorded into a HIP graph.
+
+  A replay runs the recorded kernels, which may write user tensors (a recorded momentum update does) without any
+  tensor's version changing: every replay therefore forgets the cached rankings of gars.py, like every other routine of
+  the package that writes user tensors.  An eager rule after a replay ranks the contents it finds."""
 
   def __init__(self, fn, warmup=2):
     if not torch.cuda.is_available():
@@ -78,5 +82,6 @@ class GraphedCall:
     self._stream = side
 
   def __call__(self):
+    gars.invalidate_rank_cache()  # (the recorded kernels may write anything: no ranking of earlier contents survives)
     self._graph.replay()
     return self.output
