@@ -14,12 +14,13 @@ Reference semantics, per rule:
 """
 
 import ctypes
-import math
 import weakref
 
 import torch
 
-from . import _lib
+from . import _lib, pipelines
+from .pipelines import (BRUTE_NO_SUBSET, FORMS, NNM_RULES, SCALAR_RULES, GarInputError,  # noqa: F401  (theirs, kept here)
+                        check_center_args, check_spectral_args)
 
 __all__ = ["median", "trmean", "phocas", "meamed", "krum", "bulyan", "brute", "aksel", "average", "cge",
            "krum_selection", "bulyan_ranking", "brute_selection", "aksel_selection", "cge_selection",
@@ -27,10 +28,6 @@ __all__ = ["median", "trmean", "phocas", "meamed", "krum", "bulyan", "brute", "a
            "stable_argsort", "GarInputError", "geomed", "cclip", "center_weights", "weighted_sum",
            "nnm", "bucketing", "nnm_masks", "mix_rows", "nnm_rows", "colwise_mixed", "bucket_masks", "NNM_RULES",
            "mixed_sqdist", "mix_weights", "SCALAR_RULES", "caf", "dnc", "spectral_weights"]
-
-
-class GarInputError(ValueError):
-  """The gradients cannot be served by the HIP path (wrong device, dtype, layout or count)."""
 
 
 # ---------------------------------------------------------------------------- #
@@ -298,17 +295,10 @@ def _brute_sel(gradients, f):
 def brute_selection(gradients, f, **kwargs):
   """Index set (ascending) of the n-f rows of smallest diameter (aggregators/brute.py:32-68) — host list,
   synchronises; raises when no subset of n-f rows has a finite diameter (the reference then has no selection)."""
-  n = len(gradients)
-  sel, status = _brute_sel(gradients, f)
-  if int(status.item()) == -2:  # the device search gave up: the host search has no budget
-    sel = brute_host_selection(gradients, f)
-    _rank_cache_put("brute", gradients, (f,), (sel, torch.zeros(1, dtype=torch.int32, device=sel.device)))
-  else:
-    brute_check(status)
-  return sel[:n - f].tolist()
+  sel, _ = _brute_resolved(gradients, f, *_brute_sel(gradients, f), True)
+  return sel[:len(gradients) - f].tolist()
 
 
-BRUTE_NO_SUBSET = "brute: too many non-finite gradients, no subset of n-f rows has a finite diameter"
 BRUTE_BUDGET = ("brute: the device search gave up after its budget of search-tree nodes (csrc/brute.hip; a distance matrix "
                 "built against the search?) — gars.brute_select_host on the host has no such limit")
 # (convenience only: the status of the latest brute() of this PROCESS, whatever its device or stream; the status of a
@@ -336,10 +326,18 @@ def brute_host_selection(gradients, f, sq=None):
   n, d, device = _validate(gradients)
   if sq is None:
     sq = pairwise_sqdist(gradients)
-  sel = brute_select_host(sq.sqrt().cpu().contiguous(), n, f)
-  table = torch.zeros(_lib.MAX_ROWS, dtype=torch.int32)
-  table[:n - f] = torch.tensor(sel, dtype=torch.int32)
-  return table.to(device)
+  return _legs.host_selection(sq, n, f, gradients[0])
+
+
+def _brute_resolved(gradients, f, sel, status, check):
+  """The (sel, status) of _brute_sel through the status protocol (pipelines.brute_resolve); a host re-search replaces
+  the cache entry, its status a zero."""
+  sel, status = pipelines.brute_resolve(sel, status, None, len(gradients), f, check,
+                                        lambda *_: brute_host_selection(gradients, f))
+  if status is None:
+    status = torch.zeros(1, dtype=torch.int32, device=sel.device)
+    _rank_cache_put("brute", gradients, (f,), (sel, status))
+  return sel, status
 
 
 def brute(gradients, f, check=False, **kwargs):
@@ -357,18 +355,10 @@ def brute(gradients, f, check=False, **kwargs):
   global last_brute_status
   n, d, device = _validate(gradients)
   sel, status = _brute_sel(gradients, f)
-  last_brute_status = status
-  if check and not torch.cuda.is_current_stream_capturing():
-    code = int(status.item())
-    if code == -2:
-      sel = brute_host_selection(gradients, f)
-      status = torch.zeros(1, dtype=torch.int32, device=device)
-      _rank_cache_put("brute", gradients, (f,), (sel, status))
-      last_brute_status = status
-    elif code != 0:
-      raise RuntimeError(BRUTE_NO_SUBSET)
+  last_brute_status = status  # (what a refusal below leaves behind)
+  sel, last_brute_status = _brute_resolved(gradients, f, sel, status, check)
   out = selected_mean(gradients, sel, n - f)
-  out.brute_status = status
+  out.brute_status = last_brute_status
   return out
 
 
@@ -431,19 +421,6 @@ def average(gradients, **kwargs):
 # ---------------------------------------------------------------------------- #
 # Geometric median and centered clipping: one distance pass, the iteration on scalars, one weighted sum
 
-def check_center_args(mode, param, iters, tol):
-  """The arguments bm_center_weights refuses, refused here with their names (a ValueError)."""
-  name = {"geomed": "nu", "cclip": "tau"}.get(mode)
-  if name is None:
-    raise ValueError(f"unknown mode {mode!r} (geomed, cclip)")
-  if isinstance(param, bool) or not isinstance(param, (int, float)) or not (0 < param < float("inf")):
-    raise ValueError(f"{mode}: {name} must be a positive finite number, got {param!r}")
-  if isinstance(iters, bool) or not isinstance(iters, int) or not 1 <= iters <= _lib.CENTER_MAX_ITERS:
-    raise ValueError(f"{mode}: iters must be an integer within 1..{_lib.CENTER_MAX_ITERS}, got {iters!r}")
-  if isinstance(tol, bool) or not isinstance(tol, (int, float)) or not (0 <= tol < float("inf")):
-    raise ValueError(f"{mode}: tol must be a finite number >= 0, got {tol!r}")
-
-
 def center_weights(sq, n, mode, param, iters, tol=0.0, has_start=False):
   """The weights of the geometric median ("geomed", param = nu) or of centered clipping ("cclip", param = tau) from the
   N x N squared distances of the n rows (+ the start vector as point n when has_start), N = n + has_start <= 64 — the
@@ -488,15 +465,7 @@ def weighted_sum(gradients, weights):
 
 
 def _center(mode, gradients, param, iters, tol, start):
-  points = list(gradients) + ([start] if start is not None else [])
-  n = len(gradients)
-  if len(points) > _lib.MAX_ROWS:
-    raise GarInputError(f"{mode}: at most {_lib.MAX_ROWS} gradients are supported"
-                        f"{' (one fewer with a start vector)' if start is not None else ''}, got {n}")
-  check_center_args(mode, param, iters, tol)
-  _validate(points)
-  weights, _ = center_weights(pairwise_sqdist(points), n, mode, param, iters, tol, start is not None)
-  return weighted_sum(points, weights)
+  return pipelines.center(_legs, pairwise_sqdist, mode, gradients, param, iters, tol, start)[0]
 
 
 def geomed(gradients, f=None, nu=1e-6, iters=8, tol=0.0, **kwargs):
@@ -512,30 +481,11 @@ def cclip(gradients, f=None, tau=None, iters=3, tol=0.0, start=None, **kwargs):
   the gradients, e.g. the previous aggregate; None: the mean of the rows).  One distance pass over the rows and the
   start, the iteration on scalars, one weighted sum.  `tau` is required; `f` is accepted and ignored.  n <= 64 without a
   start, 63 with one."""
-  if tau is None:
-    raise ValueError("cclip: tau (the clipping radius) is required")
   return _center("cclip", gradients, tau, iters, tol, start)
 
 
 # ---------------------------------------------------------------------------- #
 # Spectral filtering (CAF, DnC): one distance pass, the filter on scalars, one weighted sum
-
-def check_spectral_args(mode, n, count, power_iters):
-  """The arguments bm_spectral_weights refuses, refused here with their names (a ValueError)."""
-  name = {"caf": "f", "dnc": "k"}.get(mode)
-  if name is None:
-    raise ValueError(f"unknown mode {mode!r} (caf, dnc)")
-  if isinstance(count, bool) or not isinstance(count, int) or count < 0:
-    raise ValueError(f"{mode}: {name} must be an integer >= 0, got {count!r}")
-  if mode == "caf" and not 2 * count < n:
-    raise ValueError(f"caf: 2 f < n is needed, got f = {count} with n = {n}")
-  if mode == "dnc" and not count < n:
-    raise ValueError(f"dnc: k < n is needed, got k = {count} with n = {n}")
-  if (isinstance(power_iters, bool) or not isinstance(power_iters, int)
-      or not 1 <= power_iters <= _lib.SPECTRAL_MAX_POWER_ITERS):
-    raise ValueError(f"{mode}: power_iters must be an integer within 1..{_lib.SPECTRAL_MAX_POWER_ITERS}, "
-                     f"got {power_iters!r}")
-
 
 def spectral_weights(sq, n, mode, count, power_iters=16):
   """The weights of CAF ("caf", count = f) or DnC ("dnc", count = k rows to remove) from the n x n squared distances of
@@ -562,14 +512,8 @@ def spectral_weights(sq, n, mode, count, power_iters=16):
 
 
 def _spectral(mode, gradients, count, power_iters):
-  n = len(gradients)
-  if n > _lib.MAX_ROWS:
-    raise GarInputError(f"{mode}: at most {_lib.MAX_ROWS} gradients are supported, got {n}")
-  check_spectral_args(mode, n, count, power_iters)
-  _validate(gradients)
-  weights, info = spectral_weights(pairwise_sqdist(gradients), n, mode, count, power_iters)
-  out = weighted_sum(gradients, weights)
-  out.spectral_weights, out.spectral_info = weights, info
+  out, record = pipelines.spectral(_legs, pairwise_sqdist, mode, gradients, count, power_iters)
+  out.spectral_weights, out.spectral_info = record.weights, record.info
   return out
 
 
@@ -590,13 +534,7 @@ def dnc(gradients, f, c=1.0, power_iters=16, **kwargs):
   on the top eigen-direction of the rows' covariance are removed, the output is the mean of the others.  One distance
   pass, the projections on the n x n distances, one weighted sum; no host synchronisation.  n <= 64.  The result carries
   `.spectral_weights` and `.spectral_info` (device tensors)."""
-  n = len(gradients)
-  if isinstance(f, bool) or not isinstance(f, int) or f < 0:
-    raise ValueError(f"dnc: f must be an integer >= 0, got {f!r}")
-  if isinstance(c, bool) or not isinstance(c, (int, float)) or not (0 <= c < float("inf")):
-    raise ValueError(f"dnc: c must be a finite number >= 0, got {c!r}")
-  k = min(int(math.ceil(c * f)), max(n - 1, 0))
-  return _spectral("dnc", gradients, k, power_iters)
+  return _spectral("dnc", gradients, pipelines.dnc_count(len(gradients), f, c), power_iters)
 
 
 # ---------------------------------------------------------------------------- #
@@ -673,11 +611,6 @@ def nnm_rows(gradients, f):
   (one distance pass, the masks on the device, one mixing pass; no host synchronisation)."""
   n, d, device = _validate(gradients)
   return mix_rows(gradients, nnm_masks(pairwise_sqdist(gradients), n, f), n)
-
-
-# the rules nnm / bucketing can run on the mixed rows, and whether they take f
-NNM_RULES = {"median": False, "trmean": True, "phocas": True, "meamed": True, "krum": True, "bulyan": True, "brute": True,
-             "aksel": True, "cge": True, "average": False, "geomed": False, "cclip": False, "caf": True, "dnc": True}
 
 
 def _rule_on(rule, rows, f, rule_args):
@@ -765,89 +698,42 @@ def mix_weights(masks, n_in, n_out, weights=None, selection=None, m=None):
   return out
 
 
-# the rules form="scalars" serves: their output on mixed rows needs the distances between mixed rows and a weighted sum
-# of the original rows, nothing else
-SCALAR_RULES = ("krum", "brute", "geomed", "cclip", "average")
-FORMS = ("rows", "scalars")
+class _Legs:
+  """The launching functions of this module as the pipelines call them, looked up in the module at CALL time (a test
+  that replaces one sees its calls)."""
+
+  def __getattr__(self, name):
+    return globals()[name]
+
+  def rank(self, sq, n, f, m, mode):
+    return rank_from_sqdist(sq, n, f, m, mode)[0]
+
+  def host_selection(self, sq, n, f, like):
+    """The host Brute search (no node budget) on the squared distances `sq`, as a device index table."""
+    table = torch.zeros(_lib.MAX_ROWS, dtype=torch.int32)
+    table[:n - f] = torch.tensor(brute_select_host(sq.sqrt().cpu().contiguous(), n, f), dtype=torch.int32)
+    return table.to(like.device)
 
 
-def _check_form(where, form, rule):
-  if form not in FORMS:
-    raise ValueError(f"{where}: unknown form {form!r} ({', '.join(FORMS)})")
-  if form == "scalars" and rule not in SCALAR_RULES:
-    raise ValueError(f"{where}: form='scalars' serves {', '.join(SCALAR_RULES)} only, got rule {rule!r}")
+_legs = _Legs()
 
 
 def _rule_on_scalars(where, gradients, rule, n_out, masks_from, need_sq, rule_args):
-  """`rule` on the n_out mixed rows of `gradients` without writing one: distances of the ORIGINAL rows (and of a cclip
-  start, point n) -> masks_from(that n x n matrix, or None when neither the masks nor the rule read distances) ->
-  mixed_sqdist -> the rule's own scalar stage -> mix_weights -> weighted_sum.  Launches on the current stream only;
-  the one synchronisation is brute's with check=True.  The result carries `mix_masks`, `mix_weights` and, for krum and
-  brute, `mix_selection` = (index tensor, count)."""
+  """`rule` on the n_out mixed rows of `gradients` without writing one (pipelines.on_scalars): launches on the current
+  stream only; the one synchronisation is brute's with check=True.  The result carries `mix_masks`, `mix_weights` and,
+  for krum and brute, `mix_selection` = (index tensor, count)."""
   global last_brute_status
   n, d, device = _validate(gradients)
-  args = dict(rule_args)
-  takes_f = NNM_RULES[rule]
-  if takes_f and "f" not in args:
+  if NNM_RULES[rule] and "f" not in rule_args:
     raise TypeError(f"{where}: {rule} needs f (the rule's f on the {n_out} mixed rows)")
-  f = args.pop("f", None)
-  points, start, selection = list(gradients), None, None
-  if rule in ("geomed", "cclip"):
-    mode = rule
-    if rule == "geomed":
-      param, iters = args.pop("nu", 1e-6), args.pop("iters", 8)
-    else:
-      param, iters, start = args.pop("tau", None), args.pop("iters", 3), args.pop("start", None)
-      if param is None:
-        raise ValueError("cclip: tau (the clipping radius) is required")
-    tol = args.pop("tol", 0.0)
-    check_center_args(mode, param, iters, tol)
-    if start is not None:
-      points.append(start)
-      if n_out + 1 > _lib.MAX_ROWS or n + 1 > _lib.MAX_ROWS:
-        raise GarInputError(f"cclip: at most {_lib.MAX_ROWS - 1} gradients are supported with a start vector, got {n}")
-      _validate(points)
-  sq = None
-  if need_sq or rule != "average":
-    sq = pairwise_sqdist(points)
-  masks = masks_from(sq if start is None or sq is None else sq[:n, :n].contiguous())
-  n_in = len(points)
-  if start is not None:  # the start is point n of the pass and mixed row n_out, alone in its mask
-    own = torch.full((1,), (1 << n) - (1 << 64 if n == 63 else 0), dtype=torch.int64, device=device)
-    masks = torch.cat((masks[:n_out], own))
-  if rule == "average":
-    weights = torch.full((_lib.MAX_ROWS,), 1.0 / n_out, dtype=torch.float64, device=device)
-    w = mix_weights(masks, n_in, n_out, weights=weights)
-  else:
-    mixed = mixed_sqdist(sq, n_in, masks, n_out + (start is not None))
-    if rule == "krum":
-      m = args.pop("m", None)
-      if m is None:
-        m = n_out - f - 2
-      order, _ = rank_from_sqdist(mixed, n_out, f, m, _lib.RANK_KRUM)
-      selection = (order, m)
-    elif rule == "brute":
-      sel, status = brute_select_device(mixed, n_out, f)
-      last_brute_status = status
-      if args.pop("check", False) and not torch.cuda.is_current_stream_capturing():
-        code = int(status.item())
-        if code == -2:  # the device search gave up: the host search has no budget
-          table = torch.zeros(_lib.MAX_ROWS, dtype=torch.int32)
-          table[:n_out - f] = torch.tensor(brute_select_host(mixed.sqrt().cpu().contiguous(), n_out, f), dtype=torch.int32)
-          sel, status = table.to(device), torch.zeros(1, dtype=torch.int32, device=device)
-          last_brute_status = status
-        elif code != 0:
-          raise RuntimeError(BRUTE_NO_SUBSET)
-      selection = (sel, n_out - f)
-    if selection is not None:
-      w = mix_weights(masks, n_in, n_out, selection=selection[0], m=selection[1])
-    else:
-      weights, _ = center_weights(mixed, n_out, mode, param, iters, tol, start is not None)
-      w = mix_weights(masks, n_in, n_out + (start is not None), weights=weights)
-  out = weighted_sum(points, w)
-  out.mix_masks, out.mix_weights, out.mix_selection = masks, w, selection
+  out, record = pipelines.on_scalars(_legs, pairwise_sqdist, gradients, rule, rule_args.get("f"), n_out, masks_from,
+                                     need_sq, rule_args)
+  out.mix_masks, out.mix_weights, out.mix_selection = record.masks_read, record.weights, record.selection
   if rule == "brute":
-    out.brute_status = status
+    status = record.brute_status
+    if status is None:  # (a host re-search)
+      status = torch.zeros(1, dtype=torch.int32, device=device)
+    last_brute_status = out.brute_status = status
   return out
 
 
@@ -863,9 +749,7 @@ def nnm(gradients, f, rule="trmean", form="rows", **rule_args):
   rule's scalar stage runs on them, and its output is ONE weighted sum of the original rows (mix_weights, weighted_sum) —
   the same selection as form="rows" wherever the rule's decisions are not within the distance pass's error of a tie.
   No host synchronisation (graph-capturable) where the rule has none.  An unknown rule raises ValueError."""
-  if rule not in NNM_RULES:
-    raise ValueError(f"nnm: unknown rule {rule!r} ({', '.join(sorted(NNM_RULES))})")
-  _check_form("nnm", form, rule)
+  pipelines.check_rule_form("nnm", rule, form)
   n, d, device = _validate(gradients)
   if form == "scalars":
     if NNM_RULES[rule]:
@@ -902,9 +786,7 @@ def bucketing(gradients, s, rule, seed=None, perm=None, form="rows", **rule_args
   ceil(n / s) means contain a Byzantine row, so the rule has to be admissible for that f on that many rows.
   form="scalars" (SCALAR_RULES only) writes no bucket mean: one distance pass over the rows (none for "average"), the
   rule's scalar stage on the distances between the means (mixed_sqdist), one weighted sum of the rows."""
-  if rule not in NNM_RULES:
-    raise ValueError(f"bucketing: unknown rule {rule!r} ({', '.join(sorted(NNM_RULES))})")
-  _check_form("bucketing", form, rule)
+  pipelines.check_rule_form("bucketing", rule, form)
   n, d, device = _validate(gradients)
   s = int(s)
   if not 1 <= s <= n:

@@ -27,7 +27,13 @@ import warnings
 import torch
 import torch.distributed as dist
 
-from . import _lib
+from . import _lib, gars, pipelines, stats
+from .torch_legs import Legs
+# the stand-ins lived here before torch_legs.py: their names stay importable from this module for callers that predate it
+from .torch_legs import (_anticge_scale_torch, _anticge_sum_torch, _attack_vector_torch,  # noqa: F401
+                         _center_weights_torch, _mask_words, _minmax_factor_torch, _mix_rows_torch, _mix_weights_torch,
+                         _mixed_sqdist_torch, _nnm_masks_torch, _perturb_stats_torch, _spectral_weights_torch,
+                         _weighted_sum_torch)
 
 __all__ = ["shard_bounds", "owned_workers", "Shards", "ShardedAggregator", "HipBackend", "NativeComm"]
 
@@ -117,7 +123,6 @@ class HipBackend:
     "mixed_sqdist", "mix_weights", "spectral_weights", "perturb_stats", "minmax_factor"))
 
   def __init__(self):
-    from . import gars, stats
     self.gars = gars
     self.stats = stats
 
@@ -318,361 +323,6 @@ class HipBackend:
     return self.stats.step_worker(comm, *args, **kwargs)
 
 
-def _anticge_sum_torch(backend, local, f_decl, sq):
-  """bm_anticge_sum in plain torch for a backend without the kernel: (S, order, [sum S^2 here, |g_(maxpos)|^2])."""
-  h = len(local)
-  maxpos = h - f_decl
-  keys = torch.where(torch.isfinite(sq[:h]), sq[:h], torch.full_like(sq[:h], math.inf))
-  order = backend.argsort(keys, h)
-  ranked = order[:h].tolist()
-  attack = local[ranked[0]].clone()
-  for i in ranked[:maxpos]:  # (the smallest row a second time first: anticge.py:70-72)
-    attack.add_(local[i])
-  return attack, order, torch.stack([attack.double().pow(2).sum(), keys[ranked[maxpos]]])
-
-
-def _anticge_scale_torch(vec, scal):
-  """bm_anticge_scale in plain torch: the norms as fp32 numbers, nextafter and quotient in double (anticge.py:68,74-76)."""
-  attnorm, byznorm = scal.sqrt().float().tolist()
-  if attnorm > 0:
-    vec.mul_(-math.nextafter(byznorm, 0) / attnorm)
-  return vec
-
-
-def _perturb_stats_torch(backend, local, perturbation):
-  """bm_perturb_stats in plain torch for a backend without the kernel: the backend's sequential fp32 average, the
-  direction in fp32, the scalars as fp64 sums of the fp32 vectors."""
-  h = len(local)
-  avg = backend.stack_stats(local)[0]
-  if perturbation == "unit":
-    direction = avg.neg()
-  elif perturbation == "std":
-    direction = torch.stack(list(local)).var(dim=0).sqrt_().neg_() if avg.numel() else avg.clone()
-  else:
-    direction = torch.sign(avg).neg_()
-  p64, a64 = direction.double(), avg.double()
-  scal = torch.zeros(_lib.PERTURB_SLOTS, dtype=torch.float64, device=avg.device)
-  for i in range(h):
-    scal[i] = torch.dot(p64, a64 - local[i].double())
-  scal[_lib.PERTURB_P], scal[_lib.PERTURB_N] = torch.dot(p64, p64), torch.dot(a64, a64)
-  return avg, direction, scal
-
-
-def _minmax_factor_torch(sq, scal, h, mode):
-  """bm_minmax_factor in Python floats (fp64, plain index order: the host form's arithmetic): fp64[6]."""
-  D = sq.reshape(-1)[:h * h].reshape(h, h).tolist()
-  sc = scal.tolist()
-  b, P, N = sc[:h], sc[_lib.PERTURB_P], sc[_lib.PERTURB_N]
-  rowsum = []
-  for i in range(h):
-    t = 0.0
-    for j in range(h):
-      t = t + D[i][j]
-    rowsum.append(t)
-  total = 0.0
-  for t in rowsum:
-    total = total + t
-  a = [max(rowsum[i] / h - total / (2.0 * h * h), 0.0) if not math.isnan(rowsum[i]) else math.nan for i in range(h)]
-  gamma, binding, ok = 0.0, -1.0, P > 0.0 and math.isfinite(P)
-  if mode == "minmax":
-    pairs = [D[i][j] for i in range(h) for j in range(i + 1, h)]
-    bound = math.nan if any(math.isnan(v) for v in pairs) else max(pairs)
-    ok = ok and math.isfinite(bound) and all(math.isfinite(v) for v in a + b)
-    if ok:
-      disc = [b[i] * b[i] + P * (bound - a[i]) for i in range(h)]
-      ok = all(v >= 0.0 for v in disc)
-    if ok:
-      cands = [(-b[i] + math.sqrt(disc[i])) / P for i in range(h)]
-      best = min(range(h), key=lambda i: (cands[i], i))
-      ok = math.isfinite(cands[best])
-      if ok:
-        gamma, binding = cands[best], float(best)
-  else:
-    bound = math.nan if any(math.isnan(v) for v in rowsum) else max(rowsum)
-    A = B = 0.0
-    for i in range(h):
-      A, B = A + a[i], B + b[i]
-    disc = B * B + h * P * (bound - A)
-    ok = ok and math.isfinite(bound) and math.isfinite(A) and math.isfinite(B) and disc >= 0.0
-    if ok:
-      g = (-B + math.sqrt(disc)) / (h * P)
-      ok = math.isfinite(g)
-      gamma = g if ok else 0.0
-  return torch.tensor([gamma, bound, binding, P, N, 0.0 if ok else 1.0], dtype=torch.float64, device=sq.device)
-
-
-def _attack_vector_torch(kind, avg, factor, target, want_direction):
-  """bm_attack_vector in plain torch for a backend without the kernel: the same fp32 expression at every coordinate,
-  avg + factor * dir with dir in {0, 1} (never a copy of avg), the factor rounded to fp32 first."""
-  if kind == "nan":
-    return torch.full_like(avg, math.nan)
-  if isinstance(factor, torch.Tensor):  # (a device search's float64[1]: rounded as the kernel rounds it)
-    factor = factor.reshape(-1)[0].to(avg.device, torch.float32)
-  else:
-    factor = torch.tensor(float(factor), dtype=torch.float32, device=avg.device)
-  if kind == "scale":
-    return avg * factor
-  direction = torch.ones_like(avg) if kind == "shift_all" else torch.zeros_like(avg)
-  if kind == "shift_one" and target is not None and target >= 0:
-    direction[target] = 1
-  out = avg + factor * direction
-  return (out, direction) if want_direction else out
-
-
-def _center_weights_torch(sq, n, mode, param, iters, tol, has_start):
-  """bm_center_weights in plain torch (fp64, where `sq` lives) for a backend without the kernel: the iteration of
-  include/bm_gar.h on the weights — (weights fp64[MAX_ROWS], info fp64[3])."""
-  N = n + (1 if has_start else 0)
-  D = sq[:N, :N].to(torch.float64)
-  weights = torch.zeros(_lib.MAX_ROWS, dtype=torch.float64, device=sq.device)
-  off = ~torch.eye(N, dtype=torch.bool, device=sq.device)
-  bad = (~torch.isfinite(D) & off).sum(dim=1)
-  usable = ~((bad > 0) & (2 * bad >= N - 1))
-  rows = usable.clone()
-  rows[n:] = False
-  U = int(rows.sum())
-  if U == 0:
-    weights[:N] = math.nan
-    return weights, torch.tensor([0.0, math.nan, 0.0], dtype=torch.float64, device=sq.device)
-  Dz = torch.where(torch.isfinite(D), D, torch.zeros_like(D))  # (a term of weight 0 is skipped, whatever D holds)
-  blind = ~torch.isfinite(D)
-  c = torch.zeros(N, dtype=torch.float64, device=sq.device)
-  if has_start and bool(usable[n]):
-    c[n] = 1.0
-  else:
-    c[rows] = 1.0 / U
-
-  def dot_rows(w):  # sum_j w_j D_ij with the terms of weight 0 skipped; NaN where a term that counts is not finite
-    t = Dz @ w
-    return torch.where((blind & (w != 0)[None, :]).any(dim=1), torch.full_like(t, math.nan), t)
-
-  done, move2 = 0, 0.0
-  for _ in range(iters):
-    t = dot_rows(c)
-    q = (c * torch.where(c != 0, t, torch.zeros_like(t))).sum()
-    r2 = t - 0.5 * q
-    r = torch.where(torch.isfinite(r2), r2.clamp_min(0.0).sqrt(), torch.full_like(r2, math.inf))
-    if mode == "geomed":
-      w = torch.where(rows, 1.0 / r.clamp_min(param), torch.zeros_like(r))
-      nxt = w / w.sum()
-    else:
-      s = torch.where(rows, torch.where(r <= param, torch.ones_like(r), param / r), torch.zeros_like(r))
-      nxt = c * (1.0 - s.sum() / U) + s / U
-    e = nxt - c
-    c = nxt
-    u = dot_rows(e)
-    move2 = max(0.0, -0.5 * float((e * torch.where(e != 0, u, torch.zeros_like(u))).sum()))
-    done += 1
-    if tol > 0 and math.sqrt(move2) <= tol:
-      break
-  weights[:N] = c
-  return weights, torch.tensor([float(done), move2, float(U)], dtype=torch.float64, device=sq.device)
-
-
-def _spectral_weights_torch(sq, n, mode, count, power_iters):
-  """bm_spectral_weights in plain torch (fp64, where `sq` lives) for a backend without the kernel: the filter of
-  include/bm_gar.h on the squared distances — (weights fp64[MAX_ROWS], info fp64[4])."""
-  D = sq.reshape(-1)[:n * n].reshape(n, n).to(torch.float64)
-  weights = torch.zeros(_lib.MAX_ROWS, dtype=torch.float64, device=sq.device)
-  off = ~torch.eye(n, dtype=torch.bool, device=sq.device)
-  bad = (~torch.isfinite(D) & off).sum(dim=1)
-  usable = ~((bad > 0) & (2 * bad >= n - 1))
-  U = int(usable.sum())
-
-  def info(rounds, lam, kept):
-    return torch.tensor([float(rounds), lam, float(U), float(kept)], dtype=torch.float64, device=sq.device)
-
-  if U == 0:
-    weights[:n] = math.nan
-    return weights, info(0, math.inf, -1)
-  Dz = torch.where(usable[:, None] & usable[None, :], D, torch.zeros_like(D))  # (rows without weight take no part)
-
-  def evaluate(c):  # (tau, lambda) of E(c), None when degenerate
-    C = c.sum()
-    live = c > 0
-    r = torch.where(live, (Dz @ c) / C, torch.zeros_like(c))
-    s = (c * r).sum() / C
-    key = torch.where(live, c * (r - 0.5 * s), torch.zeros_like(c)).clamp_min(0.0)
-    top = key.max()
-    if not float(top) > 0:
-      return None
-    first = int((key == top).nonzero()[0])
-    sc = c.sqrt()
-    z = torch.zeros_like(c)
-    z[first] = sc[first]
-
-    def kz(z):
-      Z = z.sum()
-      return torch.where(live, -0.5 * (Dz @ z - r * Z - (r * z).sum() + s * Z), torch.zeros_like(c))
-
-    for _ in range(power_iters):
-      w = sc * kz(z) / C
-      norm = float((w * w).sum().sqrt())
-      if not (0 < norm < math.inf):
-        break
-      z = sc * (w / norm)
-    q = kz(z)
-    zq = float((z * q).sum())
-    if not zq > 0:
-      return None
-    tau = torch.where(live, q * q, torch.zeros_like(q))
-    return torch.where(torch.isnan(tau), torch.full_like(tau, math.inf), tau), float((c * q * q).sum() / (C * zq))
-
-  c = usable.to(torch.float64)
-  best, lam_best, kept, rounds = c / U, math.inf, -1, 0
-  if mode == "caf":
-    for rnd in range(n):
-      C = float(c.sum())
-      if not C > n - 2 * count:
-        break
-      ev = evaluate(c)
-      if ev is None:
-        break
-      tau, lam = ev
-      rounds = rnd + 1
-      if lam < lam_best:
-        best, lam_best, kept = c / C, lam, rnd
-      tmax = float(tau.max())
-      if not tmax > 0:
-        break
-      ratio = torch.where(tau == tmax, torch.ones_like(tau), tau / tmax)
-      c = torch.where(c > 0, c * (1.0 - ratio), torch.zeros_like(c))
-  else:
-    ev = evaluate(c)
-    tau = torch.zeros_like(c)
-    if ev is not None:
-      tau, lam_best, kept, rounds = ev[0], ev[1], 0, 1
-    drop = max(0, count - (n - U))
-    idx = torch.arange(n, device=sq.device)
-    ahead = usable[None, :] & ((tau[None, :] > tau[:, None]) | ((tau[None, :] == tau[:, None]) & (idx[None, :] > idx[:, None])))
-    keep = usable & (ahead.sum(dim=1) >= drop)
-    best = keep.to(torch.float64) / (U - drop)
-  weights[:n] = best
-  return weights, info(rounds, lam_best, kept)
-
-
-def _weighted_sum_torch(points, weights):
-  """bm_weighted_sum in plain torch, accumulated in fp64: rows that are one tensor once, with their weights added; rows
-  of weight 0 are not read; a NaN weight gives NaN everywhere."""
-  w = weights[:len(points)].tolist()
-  if any(math.isnan(x) for x in w):
-    return torch.full_like(points[0], math.nan)
-  groups = {}
-  for p, x in zip(points, w):
-    groups.setdefault(id(p), [p, 0.0])[1] += x
-  acc = torch.zeros(points[0].shape, dtype=torch.float64, device=points[0].device)
-  for p, x in groups.values():
-    if x != 0.0:
-      acc.add_(p.double(), alpha=x)
-  return acc.to(points[0].dtype)
-
-
-def _nnm_masks_torch(sq, n, f):
-  """bm_nnm_masks in plain torch (fp64 ranking, where `sq` lives) for a backend without the kernel: row i and the
-  n - f - 1 other rows of smallest distance, ties to the lower index, NaN last (a stable sort) — int64[MAX_ROWS]."""
-  D = sq[:n, :n].to(torch.float64)
-  words = []
-  for i in range(n):
-    others = [j for j in range(n) if j != i]
-    order = torch.sort(D[i, others], stable=True).indices.tolist()  # NaN sorts last, equal keys keep their order
-    word = 1 << i
-    for t in order[:n - f - 1]:
-      word |= 1 << others[t]
-    words.append(word - (1 << 64) if word >= (1 << 63) else word)
-  return torch.tensor(words + [0] * (_lib.MAX_ROWS - n), dtype=torch.int64, device=sq.device)
-
-
-def _mix_rows_torch(rows, masks, n_out):
-  """bm_mix_rows in plain torch: per output row the sequential fp32 sum, in index order, of the rows in its mask, then
-  one division by their count.  A row outside the mask is not touched; an empty mask gives NaN."""
-  n = len(rows)
-  outs = []
-  for word in masks[:n_out].tolist():
-    members = [j for j in range(n) if (word >> j) & 1]
-    acc = torch.zeros_like(rows[0])
-    for j in members:
-      acc = acc + rows[j]
-    outs.append(acc / torch.tensor(float(len(members)), dtype=rows[0].dtype, device=rows[0].device))
-  return outs
-
-
-def _mask_words(masks, count):
-  return [int(w) & ((1 << 64) - 1) for w in masks[:count].tolist()]
-
-
-def _mixed_sqdist_torch(sq, n_in, masks, n_out):
-  """bm_mixed_sqdist for a backend without the kernel: the definition of include/bm_gar.h walked in Python floats (IEEE
-  doubles, the sums in the stated order), so the host form's bits — fp64 (n_out, n_out) where `sq` lives.  Reads the
-  matrix and the masks on the host."""
-  D = sq.reshape(-1)[:n_in * n_in].view(n_in, n_in).tolist()
-  words = _mask_words(masks, n_out)
-  if any(w >> n_in for w in words):
-    raise ValueError(f"mixed_sqdist: a mask has a bit at or above n_in = {n_in}")
-  members = [[j for j in range(n_in) if (w >> j) & 1] for w in words]
-  Q = [[0.0] * n_out for _ in range(n_in)]
-  for i in range(n_in):
-    for b in range(n_out):
-      s = 0.0
-      for j in members[b]:
-        if j != i:
-          s = s + D[min(i, j)][max(i, j)]
-      Q[i][b] = s
-
-  def P(a, b):
-    s = 0.0
-    for i in members[a]:
-      s = s + Q[i][b]
-    return s
-
-  diag = [P(a, a) for a in range(n_out)]
-  out = [[0.0] * n_out for _ in range(n_out)]
-  for a in range(n_out):
-    out[a][a] = 0.0 if words[a] else math.nan
-    for b in range(a + 1, n_out):
-      if not words[a] or not words[b]:
-        v = math.nan
-      elif words[a] == words[b]:
-        v = 0.0
-      else:
-        x, y = (a, b) if words[a] < words[b] else (b, a)  # the smaller mask word walks the outer sum
-        p, cx, cy = P(x, y), float(len(members[x])), float(len(members[y]))
-        if not (math.isfinite(p) and math.isfinite(diag[x]) and math.isfinite(diag[y])):
-          v = math.nan
-        else:
-          v = p / (cx * cy) - 0.5 * diag[x] / (cx * cx) - 0.5 * diag[y] / (cy * cy)
-          v = 0.0 if v <= 0.0 else v
-      out[a][b] = out[b][a] = v
-  return torch.tensor(out, dtype=torch.float64, device=sq.device)
-
-
-def _mix_weights_torch(masks, n_in, n_out, weights=None, selection=None, m=None):
-  """bm_mix_weights for a backend without the kernel, in Python floats: the host form's bits — fp64[MAX_ROWS] where the
-  weights / the selection live."""
-  given = weights if weights is not None else selection
-  words = _mask_words(masks, n_out)
-  if any(w >> n_in for w in words):
-    raise ValueError(f"mix_weights: a mask has a bit at or above n_in = {n_in}")
-  ok = True
-  if selection is not None:
-    sel = [int(t) for t in selection[:m].tolist()]
-    ok = all(0 <= t < n_out for t in sel)
-    w = [0.0] * n_out
-    if ok:
-      for t in sel:
-        w[t] = w[t] + 1.0 / float(m)
-  else:
-    w = weights[:n_out].tolist()
-  ok = ok and all(w[r] == 0.0 or words[r] for r in range(n_out))
-  out = [0.0] * _lib.MAX_ROWS
-  for j in range(n_in):
-    s = 0.0
-    for r in range(n_out):
-      if w[r] != 0.0 and (words[r] >> j) & 1:
-        s = s + w[r] / float(bin(words[r]).count("1"))
-    out[j] = s if ok else math.nan
-  return torch.tensor(out, dtype=torch.float64, device=given.device)
-
-
 class ShardedAggregator:
   """Aggregation rules over gradients whose coordinates are sharded across the ranks of `group`."""
 
@@ -683,6 +333,7 @@ class ShardedAggregator:
     local_only: a single-rank aggregator whatever the state of torch.distributed (the whole vectors are here:
     no collective is ever issued) — e.g. the unsharded reference computation inside a multi-rank job."""
     self.backend = backend if backend is not None else HipBackend()
+    self.legs = Legs(self.backend)  # every optional leg, the backend's or its plain-torch stand-in: resolved once
     self.group = group
     initialised = dist.is_available() and dist.is_initialized() and not local_only
     self.world_size = dist.get_world_size(group) if initialised else 1
@@ -934,32 +585,15 @@ class ShardedAggregator:
     search being a function of the all-reduced matrix): -1 raises like the reference (brute.py:68), -2 repeats the
     search on the host, which has no budget — AggregationStep does this before it hands out the defense vector."""
     n = len(local)
-    sq = self.global_sqdist(local, d_total)
-    if hasattr(self.backend, "brute_select_device"):
-      sel, self.brute_status = self.backend.brute_select_device(sq, n, f)
-      if check and not (sq.is_cuda and torch.cuda.is_current_stream_capturing()):
-        code = int(self.brute_status.item())
-        if code == -2:
-          host = self.backend.brute_select(sq.sqrt().cpu().contiguous(), n, f)
-          sel = self.backend.index_tensor(host, local[0])
-          self.brute_status = None
-        elif code != 0:
-          from . import gars
-          raise RuntimeError(gars.BRUTE_NO_SUBSET)
-      self.last_selection = (sel, n - f)  # (after a host re-search: the subset that is averaged, not the device's)
-      return self.backend.selected_mean(local, sel, n - f)
-    self.brute_status = None
-    sel = self.backend.index_tensor(self.backend.brute_select(sq.sqrt().cpu().contiguous(), n, f), local[0])
-    self.last_selection = (sel, n - f)
+    sel, self.brute_status = pipelines.brute_search(self.legs, self.global_sqdist(local, d_total), n, f, check, local[0])
+    self.last_selection = (sel, n - f)  # (after a host re-search: the subset that is averaged, not the device's)
     return self.backend.selected_mean(local, sel, n - f)
 
   def check_brute(self):
     """Raise when the latest unchecked brute() of THIS aggregator had no usable answer (-1: the reference's assertion,
     brute.py:68; -2: the node budget); syncs."""
-    status = getattr(self, "brute_status", None)
-    if status is not None:
-      from . import gars
-      gars.brute_check(status)
+    if self.brute_status is not None:
+      gars.brute_check(self.brute_status)
 
   def average(self, local):
     n = len(local)
@@ -974,26 +608,15 @@ class ShardedAggregator:
     return self.backend.selected_mean(local, order, n - f)
 
   def _center(self, mode, local, param, iters, tol, start, d_total):
-    """The geometric median / centered clipping of the local slice: (1) the squared distances of rows + [start],
-    all-reduced — the one collective, N x N doubles; (2) the weights of the iterate, every rank from the same matrix:
-    the same bits; (3) the weighted sum of the local slice.  No host synchronisation and no d-sized collective,
-    whatever `iters` is.  A backend that declares the "center_weights" / "weighted_sum" capabilities runs (2) / (3) as
-    kernels; any other gets the same steps in plain torch, in fp64."""
-    from . import gars
-    gars.check_center_args(mode, param, iters, tol)
-    rows = list(local)
-    points = rows + ([start] if start is not None else [])
-    if not rows or len(points) > _lib.MAX_ROWS:
-      raise gars.GarInputError(f"{mode}: 1..{_lib.MAX_ROWS} gradients are supported"
-                               f"{' (one fewer with a start vector)' if start is not None else ''}, got {len(rows)}")
-    caps = getattr(self.backend, "capabilities", ())
-    sq = self.global_sqdist(points, self._total_of(local, d_total))
-    args = (sq, len(rows), mode, param, iters, tol, start is not None)
-    weights, info = self.backend.center_weights(*args) if "center_weights" in caps else _center_weights_torch(*args)
-    self.last_weights, self.last_center_info = weights, info
-    if "weighted_sum" in caps:
-      return self.backend.weighted_sum(points, weights)
-    return _weighted_sum_torch(points, weights)
+    """The geometric median / centered clipping of the local slice (pipelines.center): (1) the squared distances of
+    rows + [start], all-reduced — the one collective, N x N doubles; (2) the weights of the iterate, every rank from the
+    same matrix: the same bits; (3) the weighted sum of the local slice.  No host synchronisation and no d-sized
+    collective, whatever `iters` is.  A backend that declares the "center_weights" / "weighted_sum" capabilities runs
+    (2) / (3) as kernels; any other gets the same steps in plain torch, in fp64 (torch_legs)."""
+    out, record = pipelines.center(self.legs, lambda points: self.global_sqdist(points, self._total_of(local, d_total)),
+                                   mode, local, param, iters, tol, start)
+    self.last_weights, self.last_center_info = record.weights, record.info
+    return out
 
   def geomed(self, local, f=None, nu=1e-6, iters=8, tol=0.0, d_total=None):
     """The geometric median by `iters` smoothed Weiszfeld iterations from the mean of the rows (gars.geomed).
@@ -1003,29 +626,17 @@ class ShardedAggregator:
   def cclip(self, local, f=None, tau=None, iters=3, tol=0.0, start=None, d_total=None):
     """Centered clipping from `start` (this rank's slice of it; None: the mean of the rows), gars.cclip.
     `self.last_weights` keeps the weights, the start's being entry n.  tau is required; f is ignored."""
-    if tau is None:
-      raise ValueError("cclip: tau (the clipping radius) is required")
     return self._center("cclip", local, tau, iters, tol, start, d_total)
 
   def _spectral(self, mode, local, count, power_iters, d_total):
-    """CAF / DnC of the local slice, as `_center`: (1) the squared distances of the rows, all-reduced — the one
-    collective; (2) the weights of the filter, every rank from the same matrix: the same bits; (3) the weighted sum of
-    the local slice.  A backend that declares the "spectral_weights" / "weighted_sum" capabilities runs (2) / (3) as
-    kernels; any other gets the same steps in plain torch, in fp64."""
-    from . import gars
-    rows = list(local)
-    if not rows or len(rows) > _lib.MAX_ROWS:
-      raise gars.GarInputError(f"{mode}: 1..{_lib.MAX_ROWS} gradients are supported, got {len(rows)}")
-    gars.check_spectral_args(mode, len(rows), count, power_iters)
-    caps = getattr(self.backend, "capabilities", ())
-    sq = self.global_sqdist(rows, self._total_of(local, d_total))
-    args = (sq, len(rows), mode, count, power_iters)
-    weights, info = (self.backend.spectral_weights(*args) if "spectral_weights" in caps
-                     else _spectral_weights_torch(*args))
-    self.last_weights, self.last_spectral_info = weights, info
-    if "weighted_sum" in caps:
-      return self.backend.weighted_sum(rows, weights)
-    return _weighted_sum_torch(rows, weights)
+    """CAF / DnC of the local slice, as `_center` (pipelines.spectral): (1) the squared distances of the rows,
+    all-reduced — the one collective; (2) the weights of the filter, every rank from the same matrix: the same bits;
+    (3) the weighted sum of the local slice.  A backend that declares the "spectral_weights" / "weighted_sum"
+    capabilities runs (2) / (3) as kernels; any other gets the same steps in plain torch, in fp64 (torch_legs)."""
+    out, record = pipelines.spectral(self.legs, lambda rows: self.global_sqdist(rows, self._total_of(local, d_total)),
+                                     mode, local, count, power_iters)
+    self.last_weights, self.last_spectral_info = record.weights, record.info
+    return out
 
   def caf(self, local, f, power_iters=16, d_total=None):
     """CAF (gars.caf) on this rank's slice.  `self.last_weights` keeps the weights (fp64[MAX_ROWS]: the n weights, then
@@ -1034,90 +645,29 @@ class ShardedAggregator:
 
   def dnc(self, local, f, c=1.0, power_iters=16, d_total=None):
     """DnC (gars.dnc) on this rank's slice: the k = min(ceil(c f), n - 1) rows of largest squared projection removed."""
-    if isinstance(f, bool) or not isinstance(f, int) or f < 0:
-      raise ValueError(f"dnc: f must be an integer >= 0, got {f!r}")
-    if isinstance(c, bool) or not isinstance(c, (int, float)) or not (0 <= c < float("inf")):
-      raise ValueError(f"dnc: c must be a finite number >= 0, got {c!r}")
-    k = min(int(math.ceil(c * f)), max(len(local) - 1, 0))
-    return self._spectral("dnc", local, k, power_iters, d_total)
+    return self._spectral("dnc", local, pipelines.dnc_count(len(local), f, c), power_iters, d_total)
 
-  NNM_RULES = ("median", "trmean", "phocas", "meamed", "krum", "bulyan", "brute", "aksel", "cge", "average", "geomed",
-               "cclip", "caf", "dnc")
-
-  SCALAR_RULES = ("krum", "brute", "geomed", "cclip", "average")
+  NNM_RULES = tuple(pipelines.NNM_RULES)
+  SCALAR_RULES = pipelines.SCALAR_RULES
 
   def _nnm_scalars(self, rows, f, rule, total, rule_args):
-    """form="scalars" of nnm: (1) the squared distances of the rows (+ a cclip start as point n), all-reduced — the ONE
-    collective; (2) on every rank from that matrix, hence with the same bits: the neighbour masks, the distances
-    between the mixed rows (mixed_sqdist), the rule's scalar stage, the weights of the original rows (mix_weights);
-    (3) the weighted sum of the local slice.  No mixed row is written and no second matrix is reduced.  A backend that
-    declares the "mixed_sqdist" / "mix_weights" capabilities runs those as kernels; any other gets them in plain
-    Python floats (fp64, the host form's bits)."""
-    from . import gars
-    caps = getattr(self.backend, "capabilities", ())
+    """form="scalars" of nnm (pipelines.on_scalars with the neighbour masks): (1) the squared distances of the rows (+ a
+    cclip start as point n), all-reduced — the ONE collective; (2) on every rank from that matrix, hence with the same
+    bits: the neighbour masks, the distances between the mixed rows (mixed_sqdist), the rule's scalar stage, the weights
+    of the original rows (mix_weights); (3) the weighted sum of the local slice.  No mixed row is written and no second
+    matrix is reduced.  A backend that declares the "mixed_sqdist" / "mix_weights" capabilities runs those as kernels;
+    any other gets them in plain Python floats (fp64, the host form's bits: torch_legs)."""
     n = len(rows)
-    args = dict(rule_args)
-    args.pop("d_total", None)
-    start, mode = None, rule if rule in ("geomed", "cclip") else None
-    if mode == "geomed":
-      param, iters = args.pop("nu", 1e-6), args.pop("iters", 8)
-    elif mode == "cclip":
-      param, iters, start = args.pop("tau", None), args.pop("iters", 3), args.pop("start", None)
-      if param is None:
-        raise ValueError("cclip: tau (the clipping radius) is required")
-    if mode is not None:
-      tol = args.pop("tol", 0.0)
-      gars.check_center_args(mode, param, iters, tol)
-    points = rows + ([start] if start is not None else [])
-    N = len(points)
-    if N > _lib.MAX_ROWS:
-      raise gars.GarInputError(f"cclip: at most {_lib.MAX_ROWS - 1} gradients are supported with a start vector, got {n}")
-    sq = self.global_sqdist(points, total)
-    sub = sq if start is None else sq[:n, :n].contiguous()
-    masks = self.backend.nnm_masks(sub, n, f) if "nnm_masks" in caps else _nnm_masks_torch(sub, n, f)
-    self.last_masks = masks
-    if start is not None:  # the start is point n and mixed row n, alone in its mask
-      own = torch.full((1,), (1 << n) - (1 << 64 if n == 63 else 0), dtype=torch.int64, device=masks.device)
-      masks = torch.cat((masks[:n], own))
-    mixed_leg = self.backend.mixed_sqdist if "mixed_sqdist" in caps else _mixed_sqdist_torch
-    weights_leg = self.backend.mix_weights if "mix_weights" in caps else _mix_weights_torch
-    if rule == "average":
-      even = torch.full((_lib.MAX_ROWS,), 1.0 / n, dtype=torch.float64, device=sq.device)
-      w = weights_leg(masks, N, n, weights=even)
-    else:
-      mixed = mixed_leg(sq, N, masks, N)
-      if rule == "krum":
-        m = args.pop("m", None)
-        if m is None:
-          m = n - f - 2
-        order = self.backend.rank(mixed, n, f, m, _lib.RANK_KRUM)
-        self.last_selection = (order, m)
-        w = weights_leg(masks, N, n, selection=order, m=m)
-      elif rule == "brute":
-        check = args.pop("check", False)
-        if hasattr(self.backend, "brute_select_device"):
-          sel, self.brute_status = self.backend.brute_select_device(mixed, n, f)
-          if check and not (mixed.is_cuda and torch.cuda.is_current_stream_capturing()):
-            code = int(self.brute_status.item())
-            if code == -2:
-              sel = self.backend.index_tensor(self.backend.brute_select(mixed.sqrt().cpu().contiguous(), n, f), rows[0])
-              self.brute_status = None
-            elif code != 0:
-              raise RuntimeError(gars.BRUTE_NO_SUBSET)
-        else:
-          self.brute_status = None
-          sel = self.backend.index_tensor(self.backend.brute_select(mixed.sqrt().cpu().contiguous(), n, f), rows[0])
-        self.last_selection = (sel, n - f)
-        w = weights_leg(masks, N, n, selection=sel, m=n - f)
-      else:
-        cargs = (mixed, n, mode, param, iters, tol, start is not None)
-        cw, info = self.backend.center_weights(*cargs) if "center_weights" in caps else _center_weights_torch(*cargs)
-        self.last_center_info = info
-        w = weights_leg(masks, N, N, weights=cw)
-    self.last_weights = w  # of the ORIGINAL rows (and the start): what the weighted sum reads
-    if "weighted_sum" in caps:
-      return self.backend.weighted_sum(points, w)
-    return _weighted_sum_torch(points, w)
+    out, record = pipelines.on_scalars(self.legs, lambda points: self.global_sqdist(points, total), rows, rule, f, n,
+                                       lambda sq: self.legs.nnm_masks(sq, n, f), True, rule_args)
+    self.last_masks, self.last_weights = record.masks_made, record.weights
+    if record.selection is not None:
+      self.last_selection = record.selection
+    if rule == "brute":
+      self.brute_status = record.brute_status
+    if record.info is not None:
+      self.last_center_info = record.info
+    return out
 
   def nnm(self, local, f, rule="trmean", d_total=None, form="rows", **rule_args):
     """Nearest-neighbour mixing, then `rule` on the mixed rows (gars.nnm), on this rank's slice: (1) the squared
@@ -1130,29 +680,19 @@ class ShardedAggregator:
     form="scalars" (krum, brute, geomed, cclip, average; any other rule raises ValueError): `_nnm_scalars` — ONE
     all-reduce, no mixed row; it also leaves `last_weights` (the weights of the original rows) and, for krum and brute,
     `last_selection`."""
-    from . import gars
-    if rule not in self.NNM_RULES:
-      raise ValueError(f"nnm: unknown rule {rule!r} ({', '.join(sorted(self.NNM_RULES))})")
-    if form not in ("rows", "scalars"):
-      raise ValueError(f"nnm: unknown form {form!r} (rows, scalars)")
-    if form == "scalars" and rule not in self.SCALAR_RULES:
-      raise ValueError(f"nnm: form='scalars' serves {', '.join(self.SCALAR_RULES)} only, got rule {rule!r}")
+    pipelines.check_rule_form("nnm", rule, form)
     rows = list(local)
     n = len(rows)
     if not 1 <= n <= _lib.MAX_ROWS or not 0 <= f < n:
       raise gars.GarInputError(f"nnm: 1 <= n <= {_lib.MAX_ROWS} and 0 <= f < n are needed, got n = {n}, f = {f}")
-    caps = getattr(self.backend, "capabilities", ())
     total = self._total_of(local, d_total)
     if form == "scalars":
       return self._nnm_scalars(rows, f, rule, total, rule_args)
-    sq = self.global_sqdist(rows, total)
-    masks = self.backend.nnm_masks(sq, n, f) if "nnm_masks" in caps else _nnm_masks_torch(sq, n, f)
-    self.last_masks = masks
-    if (rule in ("median", "trmean") and not rule_args and "colwise_mixed" in caps
+    masks = self.last_masks = self.legs.nnm_masks(self.global_sqdist(rows, total), n, f)
+    if (rule in ("median", "trmean") and not rule_args and self.legs.colwise_mixed is not None
         and n <= self.backend.colwise_mixed_max_rows()):
-      return self.backend.colwise_mixed(rule, rows, masks, f if rule == "trmean" else 0)
-    mixed = self.backend.mix_rows(rows, masks, n) if "mix_rows" in caps else _mix_rows_torch(rows, masks, n)
-    mixed = Shards(mixed, d_total=total)
+      return self.legs.colwise_mixed(rule, rows, masks, f if rule == "trmean" else 0)
+    mixed = Shards(self.legs.mix_rows(rows, masks, n), d_total=total)
     fn = getattr(self, rule)
     if rule in ("median", "average"):
       return fn(mixed, **rule_args)
@@ -1174,11 +714,7 @@ class ShardedAggregator:
       return [torch.full_like(local[0], math.nan)] * f_real
     if not 1 <= f_decl <= h:
       raise ValueError(f"anticge needs 1 <= f_decl <= {h} honest gradients, got f_decl = {f_decl}")
-    if "anticge" in getattr(self.backend, "capabilities", ()):
-      return [self.backend.anticge(local, f_decl, self._all_reduce)] * f_real
-    byz, _, scal = _anticge_sum_torch(self.backend, local, f_decl, self._all_reduce(self.backend.row_sqnorms(local)))
-    self._all_reduce(scal[:1])
-    return [_anticge_scale_torch(byz, scal)] * f_real
+    return [self.legs.anticge(local, f_decl, self._all_reduce)] * f_real
 
   def minmax(self, local_honests, f_real, mode="minmax", perturbation="std", d_total=None):
     """The Min-Max ("minmax") / Min-Sum ("minsum") attack of Shejwalkar & Houmansadr (NDSS 2021) on this rank's slice of
@@ -1198,22 +734,14 @@ class ShardedAggregator:
       raise ValueError(f"the {mode} attack needs 2 <= h <= {_lib.MAX_ROWS} honest gradients, got h = {h}")
     if f_real <= 0:
       return []
-    caps = getattr(self.backend, "capabilities", ())
-    if "perturb_stats" in caps:
-      avg, direction, scal = self.backend.perturb_stats(local, perturbation)
-    else:
-      avg, direction, scal = _perturb_stats_torch(self.backend, local, perturbation)
+    avg, direction, scal = self.legs.perturb_stats(local, perturbation)
     sq = self.backend.pairwise_sqdist(local, d_total=self._total_of(local_honests, d_total))
     if self.collective:
       both = torch.cat([sq.reshape(-1), scal])
       self._all_reduce(both)
       sq, scal = both[:h * h].view(h, h), both[h * h:]
-    if "minmax_factor" in caps:
-      info = self.backend.minmax_factor(sq, scal, h, mode)
-      factor = info  # (read by the kernel where it is)
-    else:
-      info = _minmax_factor_torch(sq, scal, h, mode)
-      factor = info[0].item()
+    info = self.legs.minmax_factor(sq, scal, h, mode)
+    factor = info if "minmax_factor" in self.legs.native else info[0].item()  # (a kernel reads it where it is)
     byz = torch.empty_like(avg)
     self.backend.multi_fma3([byz], [avg], [direction], 1.0, factor)
     byz.attack_factor, byz.attack_info = info[:1], info
@@ -1243,9 +771,7 @@ class ShardedAggregator:
       lo, hi = shard_bounds(total, self.world_size, self.rank)
       where = target_idx % total
       target = where - lo if lo <= where < hi else -1
-    if "attack_vector" in getattr(self.backend, "capabilities", ()):
-      return self.backend.attack_vector(kind, local_avg, factor, target, want_direction)
-    return _attack_vector_torch(kind, local_avg, factor, target, want_direction)
+    return self.legs.attack_vector(kind, local_avg, factor, target, want_direction)
 
   def compute_avg_dev_max(self, local_samples):
     """Sharded tools.compute_avg_dev_max: (local slice of the average, norm, deviation, max)."""

@@ -241,7 +241,7 @@ def _worker(rank, world, port, queue):
   os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
   dist.init_process_group("gloo", rank=rank, world_size=world)
   try:
-    from byzantinemomentum_amd import sharded
+    from byzantinemomentum_amd import sharded, torch_legs
     from tests.sharded_backend import OracleBackend
     out = {}
     for ci, (kind, n, f, d, f_decl) in enumerate(SHARDED):
@@ -251,7 +251,7 @@ def _worker(rank, world, port, queue):
       agg = _Counting.make(OracleBackend())
       assert agg.collective
       sq = agg._all_reduce(agg.backend.row_sqnorms(local))
-      total, _, _ = sharded._anticge_sum_torch(agg.backend, local, f_decl, sq)   # the unscaled sum of this slice
+      total, _, _ = torch_legs._anticge_sum_torch(agg.backend, local, f_decl, sq)   # the unscaled sum of this slice
       agg.reduced = []
       res = agg.anticge(local, f_decl, f)
       assert len(res) == f and all(r is res[0] for r in res) and all(res[0] is not g for g in local)

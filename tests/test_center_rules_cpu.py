@@ -64,7 +64,7 @@ def test_torch_leg_equals_the_host_form_on_crafted_matrices():
   """The plain torch leg follows the library's definition: same weights as bm_center_weights (to rounding), the same
   exclusions, NaN when no row is usable."""
   from byzantinemomentum_amd import _lib
-  from byzantinemomentum_amd.sharded import _center_weights_torch
+  from byzantinemomentum_amd.torch_legs import _center_weights_torch
   lib = _lib.load()
   case = cc.cases()[0]
   rows, start = cc.make_rows(case)

@@ -240,7 +240,7 @@ def _rows32(h, d, structure, seed):
 @pytest.mark.parametrize("mode", R.MODES)
 @pytest.mark.parametrize("perturbation", R.PERTURBATIONS)
 def test_torch_legs_against_the_float64_reference(mode, perturbation):
-  from byzantinemomentum_amd import sharded
+  from byzantinemomentum_amd import sharded, torch_legs
   from tests.sharded_backend import OracleBackend
   for h, d, structure in ((2, 9, "iid"), (9, 130, "common"), (20, 67, "scaled")):
     rows = _rows32(h, d, structure, 5)
@@ -250,7 +250,7 @@ def test_torch_legs_against_the_float64_reference(mode, perturbation):
     assert len(res) == 3 and all(r is res[0] for r in res) and all(res[0] is not g for g in rows)
     assert all(torch.equal(a, b) for a, b in zip(kept, rows))
     byz = res[0]
-    avg, direction, scal = sharded._perturb_stats_torch(agg.backend, rows, perturbation)
+    avg, direction, scal = torch_legs._perturb_stats_torch(agg.backend, rows, perturbation)
     rows64 = np.stack([g.double().numpy() for g in rows])
     assert np.array_equal(avg.numpy(), R.seq_mean32(rows64.astype(np.float32)))
     # the legs' own fp32 average and direction, upcast: only fp64 rounding is left

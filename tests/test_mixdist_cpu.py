@@ -478,7 +478,7 @@ def test_sharded_scalars_on_one_rank():
 
 
 def test_torch_legs_give_the_host_forms_bits(bm):
-  from byzantinemomentum_amd.sharded import _mix_weights_torch, _mixed_sqdist_torch
+  from byzantinemomentum_amd.torch_legs import _mix_weights_torch, _mixed_sqdist_torch
   for n in (1, 7, 25, 64):
     sq = torch.from_numpy(np.ascontiguousarray(_matrix(n, seed=n)))
     for name, words in mc.mask_sets(n):

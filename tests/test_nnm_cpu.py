@@ -123,7 +123,7 @@ def test_python_layer_refuses_before_the_gpu(bm):
 
 @pytest.mark.parametrize("n,d", [(1, 5), (7, 1027), (25, 130), (64, 33)])
 def test_torch_mixing_is_the_float32_loop(n, d):
-  from byzantinemomentum_amd.sharded import _mix_rows_torch, _nnm_masks_torch
+  from byzantinemomentum_amd.torch_legs import _mix_rows_torch, _nnm_masks_torch
   rows = nc.random_rows(n, d, seed=n)
   if n >= 7:
     rows[2] = np.full(d, np.nan, dtype=np.float32)
@@ -147,7 +147,7 @@ def test_torch_mixing_is_the_float32_loop(n, d):
 
 @pytest.mark.parametrize("case", [c for c in nc.mask_cases() if c[2] <= 25], ids=lambda c: c[0])
 def test_torch_masks_follow_the_contract(case):
-  from byzantinemomentum_amd.sharded import _nnm_masks_torch
+  from byzantinemomentum_amd.torch_legs import _nnm_masks_torch
   name, sq, n, f = case
   words = nc.from_int64(_nnm_masks_torch(torch.from_numpy(np.ascontiguousarray(sq)), n, f).tolist())
   assert words[:n] == nc.masks_reference(sq, n, f), name

@@ -167,7 +167,7 @@ def test_torch_leg_equals_the_host_form():
   """The plain torch leg follows the library's definition: the weights of bm_spectral_weights within 1e-12, the same
   rounds, the same exclusions, NaN when no row is usable."""
   from byzantinemomentum_amd import _lib
-  from byzantinemomentum_amd.sharded import _spectral_weights_torch
+  from byzantinemomentum_amd.torch_legs import _spectral_weights_torch
   lib = _lib.load()
   items = [(sc.case_id(case) + "-" + mode, sc.exact_sqdist(sc.make_rows(case)[0]), case.n, mode, case.k)
            for case in sc.cases()[::3] for mode in ("caf", "dnc")]
