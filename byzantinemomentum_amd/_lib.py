@@ -212,6 +212,12 @@ SIGNATURES = {
   "bm_colwise_mixed": (ctypes.c_int, [ctypes.c_int, _c_float_pp, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
                                       ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
   "bm_colwise_mixed_max_rows": (ctypes.c_int, []),
+  "bm_colwise_bucketed_supported": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+  "bm_colwise_bucketed": (ctypes.c_int, [ctypes.c_int, _c_float_pp, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                         ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+  "bm_bucket_masks": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p]),
+  "bm_bucket_masks_device": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p]),
   "bm_mixed_sqdist": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
   "bm_mixed_sqdist_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                             ctypes.c_void_p]),

@@ -27,7 +27,8 @@ __all__ = ["median", "trmean", "phocas", "meamed", "krum", "bulyan", "brute", "a
            "pairwise_sqdist", "rank_from_sqdist", "selected_mean", "bulyan_pass2", "aksel_sqdist",
            "stable_argsort", "GarInputError", "geomed", "cclip", "center_weights", "weighted_sum",
            "nnm", "bucketing", "nnm_masks", "mix_rows", "nnm_rows", "colwise_mixed", "bucket_masks", "NNM_RULES",
-           "mixed_sqdist", "mix_weights", "SCALAR_RULES", "caf", "dnc", "spectral_weights"]
+           "mixed_sqdist", "mix_weights", "SCALAR_RULES", "caf", "dnc", "spectral_weights", "bucket_permutation",
+           "bucket_masks_host", "bucket_masks_device", "colwise_bucketed", "colwise_bucketed_supported"]
 
 
 # ---------------------------------------------------------------------------- #
@@ -778,10 +779,110 @@ def _masks_tensor(masks, device):
   return torch.tensor([m - (1 << 64) if m >= (1 << 63) else m for m in masks], dtype=torch.int64).to(device)
 
 
-def bucketing(gradients, s, rule, seed=None, perm=None, form="rows", **rule_args):
+_U64 = (1 << 64) - 1
+
+
+def _bucket_mix(x):
+  x ^= x >> 30
+  x = (x * 0xBF58476D1CE4E5B9) & _U64
+  x ^= x >> 27
+  x = (x * 0x94D049BB133111EB) & _U64
+  return x ^ (x >> 31)
+
+
+def bucket_permutation(n, seed, counter):
+  """The permutation of 0 .. n-1 bucketing draws from a counter (include/bm_gar.h, bm_bucket_masks), in Python integers:
+  u_i = mix(seed + 0x9E3779B97F4A7C15 * (64 * counter + i)), then for i = n-1 down to 1 swap perm[i] and
+  perm[u_i mod (i + 1)]; uint64 and wrapping throughout.  A function of (n, seed, counter) alone: no generator, no state,
+  the same list on every rank and what bm_bucket_masks / bm_bucket_masks_device cut into buckets."""
+  n, seed, counter = int(n), int(seed) & _U64, int(counter) & _U64
+  if not 1 <= n <= _lib.MAX_ROWS:
+    raise ValueError(f"bucket_permutation: 1 <= n <= {_lib.MAX_ROWS} is needed, got {n}")
+  perm = list(range(n))
+  for i in range(n - 1, 0, -1):
+    j = _bucket_mix((seed + 0x9E3779B97F4A7C15 * ((64 * counter + i) & _U64)) & _U64) % (i + 1)
+    perm[i], perm[j] = perm[j], perm[i]
+  return perm
+
+
+def _check_bucket_args(n, s):
+  n, s = int(n), int(s)
+  if not 1 <= n <= _lib.MAX_ROWS or not 1 <= s <= n:
+    raise ValueError(f"bucketing: 1 <= n <= {_lib.MAX_ROWS} and a bucket size within 1..n are needed, got n = {n}, s = {s}")
+  return n, s
+
+
+def bucket_masks_host(n, s, seed, counter):
+  """The masks bm_bucket_masks writes for (n, s, seed, counter): a host int64[MAX_ROWS] tensor, zeros beyond ceil(n / s)."""
+  n, s = _check_bucket_args(n, s)
+  masks = torch.empty(_lib.MAX_ROWS, dtype=torch.int64)
+  _lib.check(_lib.load().bm_bucket_masks(n, s, int(seed) & _U64, int(counter) & _U64, _ptr(masks)), "bm_bucket_masks")
+  return masks
+
+
+def bucket_masks_device(n, s, seed, counter_dev, out=None):
+  """The bucket masks of the counter `counter_dev` holds (a DEVICE int64[1] tensor), drawn on the device
+  (bm_bucket_masks_device: one wavefront, no synchronisation); the counter word is advanced by one, so a replayed graph
+  draws the next permutation each time.  Returns int64[MAX_ROWS] (`out` when given: a graph needs a fixed address)."""
+  n, s = _check_bucket_args(n, s)
+  if (not isinstance(counter_dev, torch.Tensor) or not counter_dev.is_cuda or counter_dev.dtype != torch.int64
+      or counter_dev.numel() < 1 or not counter_dev.is_contiguous()):
+    raise GarInputError("bucket_masks_device: the counter must be a contiguous int64 tensor on a GPU")
+  device = counter_dev.device
+  if out is None:
+    out = torch.empty(_lib.MAX_ROWS, dtype=torch.int64, device=device)
+  _check_masks(out, _lib.MAX_ROWS, "bucket_masks_device")
+  if out.device != device:
+    raise GarInputError(f"bucket_masks_device: the masks must be on {device}")
+  with torch.cuda.device(device):
+    _lib.check(_lib.load().bm_bucket_masks_device(n, s, int(seed) & _U64, _ptr(counter_dev), _ptr(out), _stream(device)),
+               "bm_bucket_masks_device")
+  return out
+
+
+def colwise_bucketed_supported(rule, n, n_out):
+  """Whether bm_colwise_bucketed has an instance for `rule` on n rows mixed into n_out."""
+  op = {"median": _lib.OP_MEDIAN, "trmean": _lib.OP_TRMEAN}.get(rule)
+  return op is not None and bool(_lib.load().bm_colwise_bucketed_supported(op, int(n), int(n_out)))
+
+
+def colwise_bucketed(rule, gradients, masks, n_out, f=0):
+  """`rule` ("median" or "trmean", f the trimmed mean's on the n_out rows) of the rows mix_rows(gradients, masks, n_out)
+  would write, without writing them (bm_colwise_bucketed): same bits.  Raises where colwise_bucketed_supported says no."""
+  n, d, device = _validate(gradients)
+  n_out = int(n_out)
+  if not 1 <= n_out <= n:
+    raise GarInputError(f"colwise_bucketed: 1 <= n_out <= {n} is needed, got {n_out}")
+  _check_masks(masks, n_out, "colwise_bucketed")
+  if masks.device != device:
+    raise GarInputError(f"colwise_bucketed: the masks must be on {device}")
+  out = torch.empty(d, dtype=torch.float32, device=device)
+  op = {"median": _lib.OP_MEDIAN, "trmean": _lib.OP_TRMEAN}[rule]
+  with torch.cuda.device(device):
+    _lib.check(_lib.load().bm_colwise_bucketed(op, _lib.pointer_table(gradients), n, _ptr(masks), n_out, d, int(f),
+                                               _ptr(out), _stream(device)), "bm_colwise_bucketed")
+  return out
+
+
+def _fused_bucketed(rule, n, n_out, rule_args):
+  """The f bm_colwise_bucketed is handed when `rule` on n rows in n_out buckets takes the fused kernel, else None: median
+  with no argument, trmean with `f` and nothing else, and an instance for the shape."""
+  if rule == "median" and not rule_args:
+    f = 0
+  elif rule == "trmean" and set(rule_args) == {"f"} and isinstance(rule_args["f"], int) and 0 <= 2 * rule_args["f"] < n_out:
+    f = rule_args["f"]
+  else:
+    return None
+  return f if colwise_bucketed_supported(rule, n, n_out) else None
+
+
+def bucketing(gradients, s, rule, seed=None, perm=None, form="rows", counter=None, **rule_args):
   """Bucketing (Karimireddy, He, Jaggi, ICLR 2022): the rows are shuffled, averaged in buckets of s, and `rule` runs on
   the ceil(n / s) bucket means.  The permutation is drawn on the host (torch generator seeded with `seed`; None: the
-  global generator) or given as `perm`, a sequence holding 0 .. n-1 once each.  One mixing pass (mix_rows), then the
+  global generator), given as `perm`, a sequence holding 0 .. n-1 once each, or — `counter` given — the counter-based
+  draw bucket_permutation(n, seed or 0, counter), the one bm_bucket_masks and its device form define to the bit.
+  median / trmean (rule_args holding nothing but trmean's `f`) where bm_colwise_bucketed has an instance: ONE kernel that
+  forms the bucket means in registers and applies the rule, the same bits; otherwise one mixing pass (mix_rows), then the
   rule's own function.  The rule's `f` is the CALLER's business — pass it in rule_args: after bucketing at most f of the
   ceil(n / s) means contain a Byzantine row, so the rule has to be admissible for that f on that many rows.
   form="scalars" (SCALAR_RULES only) writes no bucket mean: one distance pass over the rows (none for "average"), the
@@ -791,6 +892,10 @@ def bucketing(gradients, s, rule, seed=None, perm=None, form="rows", **rule_args
   s = int(s)
   if not 1 <= s <= n:
     raise ValueError(f"bucketing: the bucket size must be within 1..{n}, got {s}")
+  if counter is not None:
+    if perm is not None:
+      raise ValueError("bucketing: perm and counter exclude one another")
+    perm = bucket_permutation(n, 0 if seed is None else seed, counter)
   if perm is None:
     gen = None if seed is None else torch.Generator().manual_seed(int(seed))
     perm = torch.randperm(n, generator=gen).tolist()
@@ -801,6 +906,9 @@ def bucketing(gradients, s, rule, seed=None, perm=None, form="rows", **rule_args
   if form == "scalars":
     return _rule_on_scalars("bucketing", gradients, rule, len(masks), lambda sq: _masks_tensor(masks, device), False,
                             rule_args)
+  fused_f = _fused_bucketed(rule, n, len(masks), rule_args) if d > 0 else None
+  if fused_f is not None:
+    return colwise_bucketed(rule, gradients, _masks_tensor(masks, device), len(masks), fused_f)
   means = mix_rows(gradients, _masks_tensor(masks, device), len(masks))
   return globals()[rule](means, **rule_args)
 

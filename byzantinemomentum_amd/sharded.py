@@ -120,7 +120,8 @@ class HipBackend:
     "step_worker", "momentum_stats_colwise", "momentum_stats_sqdist", "stack_stats_colwise", "stack_stats_sqdist",
     "device_search", "attack_ranking_device", "bulyan_pass2_eval", "order_pair", "colwise_eval", "sqdist2", "anticge",
     "accept_count", "attack_vector", "center_weights", "weighted_sum", "nnm_masks", "mix_rows", "colwise_mixed",
-    "mixed_sqdist", "mix_weights", "spectral_weights", "perturb_stats", "minmax_factor"))
+    "mixed_sqdist", "mix_weights", "spectral_weights", "perturb_stats", "minmax_factor", "colwise_bucketed",
+    "bucket_masks"))
 
   def __init__(self):
     self.gars = gars
@@ -191,6 +192,20 @@ class HipBackend:
 
   def colwise_mixed(self, rule, gradients, masks, f):
     return self.gars.colwise_mixed(rule, gradients, masks, f)
+
+  def colwise_bucketed_supported(self, rule, n, n_out):
+    return self.gars.colwise_bucketed_supported(rule, n, n_out)
+
+  def colwise_bucketed(self, rule, gradients, masks, n_out, f):
+    return self.gars.colwise_bucketed(rule, gradients, masks, n_out, f)
+
+  def bucket_masks(self, n, s, seed, counter, like):
+    """The bucket masks of (n, s, seed, counter) where `like` lives, int64[MAX_ROWS].  counter: a DEVICE int64[1] tensor —
+    drawn on the device and advanced there (bm_bucket_masks_device: no synchronisation, a recorded graph draws the next
+    permutation at every replay) — or a Python integer: the host form (bm_bucket_masks), copied over."""
+    if isinstance(counter, torch.Tensor):
+      return self.gars.bucket_masks_device(n, s, seed, counter)
+    return self.gars.bucket_masks_host(n, s, seed, counter).to(like.device)
 
   def sharded_rule(self, name, comm, gradients, f, m, d_total=None, with_order=False):
     """Multi-Krum / Bulyan of the local slice in one C call (bm_sharded_krum / bm_sharded_bulyan);
@@ -650,7 +665,17 @@ class ShardedAggregator:
   NNM_RULES = tuple(pipelines.NNM_RULES)
   SCALAR_RULES = pipelines.SCALAR_RULES
 
-  def _nnm_scalars(self, rows, f, rule, total, rule_args):
+  def _sq_of(self, total, local_sq=None):
+    """points -> their all-reduced squared distances, as the pipelines ask for them.  local_sq: this rank's matrix of
+    exactly those points, already formed (the first pass of a step): reduced in place, the stand-alone pass skipped.  A
+    matrix of another row count is not that of the points asked for (a cclip start adds one) and is left unread."""
+    def sq_of(points):
+      if local_sq is not None and local_sq.shape[0] == len(points):
+        return self._all_reduce(local_sq)
+      return self.global_sqdist(points, total)
+    return sq_of
+
+  def _nnm_scalars(self, rows, f, rule, total, rule_args, local_sq=None):
     """form="scalars" of nnm (pipelines.on_scalars with the neighbour masks): (1) the squared distances of the rows (+ a
     cclip start as point n), all-reduced — the ONE collective; (2) on every rank from that matrix, hence with the same
     bits: the neighbour masks, the distances between the mixed rows (mixed_sqdist), the rule's scalar stage, the weights
@@ -658,18 +683,22 @@ class ShardedAggregator:
     matrix is reduced.  A backend that declares the "mixed_sqdist" / "mix_weights" capabilities runs those as kernels;
     any other gets them in plain Python floats (fp64, the host form's bits: torch_legs)."""
     n = len(rows)
-    out, record = pipelines.on_scalars(self.legs, lambda points: self.global_sqdist(points, total), rows, rule, f, n,
+    out, record = pipelines.on_scalars(self.legs, self._sq_of(total, local_sq), rows, rule, f, n,
                                        lambda sq: self.legs.nnm_masks(sq, n, f), True, rule_args)
     self.last_masks, self.last_weights = record.masks_made, record.weights
+    self._publish(rule, record)
+    return out
+
+  def _publish(self, rule, record):
+    """What a scalar-form pipeline decided beside its output, where this aggregator keeps it."""
     if record.selection is not None:
       self.last_selection = record.selection
     if rule == "brute":
       self.brute_status = record.brute_status
     if record.info is not None:
       self.last_center_info = record.info
-    return out
 
-  def nnm(self, local, f, rule="trmean", d_total=None, form="rows", **rule_args):
+  def nnm(self, local, f, rule="trmean", d_total=None, form="rows", local_sq=None, **rule_args):
     """Nearest-neighbour mixing, then `rule` on the mixed rows (gars.nnm), on this rank's slice: (1) the squared
     distances, all-reduced — the neighbours are those of the WHOLE vectors, the same masks on every rank; (2) mixing and
     a coordinate-wise rule are column-local: the fused kernel for median / trmean where the backend has it, else the
@@ -679,7 +708,10 @@ class ShardedAggregator:
     `self.last_masks` keeps the masks (int64[MAX_ROWS]).
     form="scalars" (krum, brute, geomed, cclip, average; any other rule raises ValueError): `_nnm_scalars` — ONE
     all-reduce, no mixed row; it also leaves `last_weights` (the weights of the original rows) and, for krum and brute,
-    `last_selection`."""
+    `last_selection`.
+    local_sq: this rank's n x n squared distances of `local`, where a caller already holds them (the first pass of a
+    step, stats.momentum_stats_sqdist): all-reduced IN PLACE as rule_from_sq does, the stand-alone distance pass skipped,
+    in either form (form="scalars" with a cclip start needs the start's distances too and runs its own pass)."""
     pipelines.check_rule_form("nnm", rule, form)
     rows = list(local)
     n = len(rows)
@@ -687,18 +719,76 @@ class ShardedAggregator:
       raise gars.GarInputError(f"nnm: 1 <= n <= {_lib.MAX_ROWS} and 0 <= f < n are needed, got n = {n}, f = {f}")
     total = self._total_of(local, d_total)
     if form == "scalars":
-      return self._nnm_scalars(rows, f, rule, total, rule_args)
-    masks = self.last_masks = self.legs.nnm_masks(self.global_sqdist(rows, total), n, f)
+      return self._nnm_scalars(rows, f, rule, total, rule_args, local_sq)
+    masks = self.last_masks = self.legs.nnm_masks(self._sq_of(total, local_sq)(rows), n, f)
     if (rule in ("median", "trmean") and not rule_args and self.legs.colwise_mixed is not None
         and n <= self.backend.colwise_mixed_max_rows()):
       return self.legs.colwise_mixed(rule, rows, masks, f if rule == "trmean" else 0)
-    mixed = Shards(self.legs.mix_rows(rows, masks, n), d_total=total)
+    return self._rule_on_rows(rule, Shards(self.legs.mix_rows(rows, masks, n), d_total=total), f, total, rule_args)
+
+  def _rule_on_rows(self, rule, mixed, f, total, rule_args):
+    """The aggregator's own `rule` on mixed rows that were written (a distance-based one all-reduces their distances)."""
     fn = getattr(self, rule)
     if rule in ("median", "average"):
       return fn(mixed, **rule_args)
     if rule in ("krum", "bulyan", "brute", "geomed", "cclip", "caf", "dnc"):
       rule_args.setdefault("d_total", total)
     return fn(mixed, f, **rule_args)
+
+  def bucketing(self, local, s, rule, seed=0, counter=None, masks=None, form="rows", d_total=None, local_sq=None,
+                **rule_args):
+    """Bucketing, then `rule` on the ceil(n / s) bucket means (gars.bucketing), on this rank's slice.  The buckets are
+    those of the counter-based draw (bm_bucket_masks: a function of n, s, seed and counter alone, so every rank draws the
+    same permutation without a collective) — `counter`: a Python integer, or a DEVICE int64[1] tensor the draw advances
+    (HipBackend.bucket_masks) — or `masks`, int64 words where the slice lives, one per bucket (at least ceil(n / s)).
+    Mixing and a coordinate-wise rule are column-local: the fused kernel for median / trmean where the backend has an
+    instance (bm_colwise_bucketed) and rule_args hold nothing but trmean's `f`, else the means are written and the
+    aggregator's own rule runs on them (a distance-based rule then all-reduces the distances of the means).  The rule's f
+    goes in rule_args, as with gars.bucketing.  form="scalars" (SCALAR_RULES) goes through pipelines.on_scalars as
+    `_nnm_scalars` does: ONE all-reduce (none for "average"), no mean written; `local_sq` as for nnm (read by this form
+    alone: form="rows" starts from no distances of the original rows and ignores it).
+    `self.last_masks` keeps the masks (int64[MAX_ROWS], or the tensor given)."""
+    pipelines.check_rule_form("bucketing", rule, form)
+    rows = list(local)
+    n, s = len(rows), int(s)
+    if not 1 <= n <= _lib.MAX_ROWS or not 1 <= s <= n:
+      raise gars.GarInputError(f"bucketing: 1 <= n <= {_lib.MAX_ROWS} and a bucket size within 1..n are needed, got "
+                               f"n = {n}, s = {s}")
+    n_out = -(-n // s)
+    if masks is None:
+      if counter is None:
+        raise ValueError("bucketing: counter (the draw's counter) or masks is needed")
+      masks = self.legs.bucket_masks(n, s, seed, counter, rows[0])
+    elif (not isinstance(masks, torch.Tensor) or masks.dtype != torch.int64 or masks.dim() != 1 or masks.numel() < n_out
+          or masks.device != rows[0].device):
+      raise gars.GarInputError(f"bucketing: masks must be an int64 tensor of at least {n_out} words where the rows live")
+    self.last_masks = masks
+    total = self._total_of(local, d_total)
+    if form == "scalars":
+      if pipelines.NNM_RULES[rule] and "f" not in rule_args:
+        raise TypeError(f"bucketing: {rule} needs f (the rule's f on the {n_out} bucket means)")
+      rule_args = dict(rule_args)
+      out, record = pipelines.on_scalars(self.legs, self._sq_of(total, local_sq), rows, rule, rule_args.pop("f", None),
+                                         n_out, lambda sq: masks, False, rule_args)
+      self.last_weights = record.weights
+      self._publish(rule, record)
+      return out
+    fused_f = None
+    if self.legs.colwise_bucketed is not None and rows[0].numel() > 0:
+      if rule == "median" and not rule_args:
+        fused_f = 0
+      elif rule == "trmean" and set(rule_args) == {"f"} and 0 <= 2 * int(rule_args["f"]) < n_out:
+        fused_f = int(rule_args["f"])
+      if fused_f is not None and not self.backend.colwise_bucketed_supported(rule, n, n_out):
+        fused_f = None
+    if fused_f is not None:
+      return self.legs.colwise_bucketed(rule, rows, masks, n_out, fused_f)
+    rule_args = dict(rule_args)
+    f = rule_args.pop("f", None)
+    mixed = Shards(self.legs.mix_rows(rows, masks, n_out), d_total=total)
+    if pipelines.NNM_RULES[rule] and f is None:
+      raise TypeError(f"bucketing: {rule} needs f (the rule's f on the {n_out} bucket means)")
+    return self._rule_on_rows(rule, mixed, f, total, rule_args)
 
   def anticge(self, local_honests, f_decl, f_real):
     """The reference's `anticge` attack (attacks/anticge.py:49-78) on this rank's slice of the honest gradients:

@@ -53,7 +53,7 @@ from typing import Any, NamedTuple, Optional
 
 import torch
 
-from . import _lib, linesearch
+from . import _lib, linesearch, pipelines
 
 __all__ = ["AggregationStep"]
 
@@ -63,6 +63,7 @@ _CENTER = {"geomed": ("nu", "iters", "tol"), "cclip": ("tau", "iters", "tol")}  
 _SPECTRAL = {"caf": ("power_iters",), "dnc": ("power_iters", "c")}               # the same for the spectral filters
 _COLWISE = ("median", "trmean", "phocas", "meamed")
 _DISTANCE = ("krum", "bulyan")
+_PRE = {"nnm": ("form",), "bucketing": ("s", "seed", "form")}  # pre-aggregation -> the `pre_args` it takes
 MAX_PAST = 4096  # past sampled averages kept for the curvature term (each is one d-vector of device memory)
 
 
@@ -137,6 +138,7 @@ class StepPlan(NamedTuple):
                                 # "direction" — at scale 1 with attack_evals, else at the fixed factor; False: a chain or
                                 # a kernel behind it forms the vector
   attack: Optional[_Attack] = None  # the row of _ATTACK
+  pre: Optional[str] = None         # the pre-aggregation in front of the rule: "nnm", "bucketing" or None
 
 
 # every scalar of the study row, from the packed vector of bm_step_worker or from the exchange of the sequence
@@ -181,7 +183,7 @@ class AggregationStep:
   def __init__(self, nb_workers, nb_decl_byz, nb_real_byz, gar="krum", gar_args=None, momentum=0.99,
                dampening=0.99, momentum_at="worker", attack="empire", attack_factor=1.1, nb_past=25,
                gradient_clip=None, aggregator=None, single_call=True, attack_evals=None, attack_negative=False,
-               line_search="auto", attack_args=None):
+               line_search="auto", attack_args=None, pre=None, pre_args=None):
     """aggregator: a sharded.ShardedAggregator (default: one over the default process group, or a
     single-rank one when torch.distributed is not initialised).
     single_call: with the HIP backend, worker-side momentum and a rule the C entry point knows
@@ -217,9 +219,48 @@ class AggregationStep:
     memory (bm_search_device_next: median, trmean, phocas, meamed, aksel, cge ...): the step then has no synchronisation
     but `floats()`; Bulyan (its candidates are ranked on the host) and Brute keep the host's cursor.  "host": the same
     forms with scalars and cursor on the host (one synchronisation per evaluation).  "generic" always runs the rule on
-    the device once per evaluation like the reference does, the cursor on the host."""
+    the device once per evaluation like the reference does, the cursor on the host.
+    pre: a pre-aggregation in front of the rule, with every rule, momentum placement, clipping and attack: "nnm" — the
+    defense is agg.nnm(stack, nb_decl_byz, rule=gar, **gar_args), every row replaced by the mean of its n - nb_decl_byz
+    nearest (ShardedAggregator.nnm) — or "bucketing": the rule runs with f = nb_decl_byz on the ceil(n / s) means of random
+    buckets of s rows (ShardedAggregator.bucketing).  pre_args: {"form": "rows" | "scalars"} for either ("scalars":
+    pipelines.SCALAR_RULES alone, no mixed row written), and for bucketing {"s": bucket size within 1..n, required,
+    "seed": default 0}.  The buckets are drawn ONCE per run(), before anything aggregates, from the step's own counter
+    (0, 1, 2 ... by step; bm_bucket_masks_device where the backend has it: the counter then lives in device memory and
+    a step replayed from a HIP graph draws the next permutation each time) — every evaluation of a factor search and the
+    final defense read the same masks, `last_masks`.  With a pre-aggregation the step is never the single call, the first
+    pass is "sqdist" where the pre-aggregated rule starts from the distances of the whole stack (nnm; bucketing with
+    form "scalars" and a rule other than average: the matrix goes in as `local_sq`) under the conditions of Krum's, else
+    "plain"; a factor search is the generic one (with the device cursor where line_search="auto" has it); there is no
+    acceptation ratio (a selection over mixed rows is not one over workers: NaN).  Unknown names, foreign keys, a form
+    the rule does not serve, pre_args without pre and a coordinate-wise rule left with fewer than 2 f + 1 rows raise
+    ValueError here."""
     if gar not in _RULES:
       raise ValueError(f"unknown aggregation rule {gar!r}")
+    if pre is None:
+      if pre_args is not None:
+        raise ValueError(f"pre_args without pre: got {pre_args!r}")
+    else:
+      if pre not in _PRE:
+        raise ValueError(f"unknown pre-aggregation {pre!r} ({', '.join(_PRE)}, or None)")
+      if gar not in pipelines.NNM_RULES:
+        raise ValueError(f"pre={pre!r} serves {', '.join(sorted(pipelines.NNM_RULES))}, got rule {gar!r}")
+      if pre_args is not None and (not isinstance(pre_args, dict) or set(pre_args) - set(_PRE[pre])):
+        raise ValueError(f"pre_args of {pre} holds {_PRE[pre]} and nothing else, got {pre_args!r}")
+      pre_args = dict(pre_args or {})
+      pipelines.check_rule_form(f"pre={pre!r}", gar, pre_args.get("form", "rows"))
+      n_out = nb_workers
+      if pre == "bucketing":
+        s = pre_args.get("s")
+        if isinstance(s, bool) or not isinstance(s, int) or not 1 <= s <= nb_workers:
+          raise ValueError(f"bucketing: pre_args must hold s, a bucket size within 1..{nb_workers}, got {s!r}")
+        seed = pre_args.get("seed", 0)
+        if isinstance(seed, bool) or not isinstance(seed, int):
+          raise ValueError(f"bucketing: seed must be an integer, got {seed!r}")
+        n_out = -(-nb_workers // s)
+      if gar in _COLWISE and n_out < 2 * nb_decl_byz + 1:
+        raise ValueError(f"{gar} behind pre={pre!r} runs on {n_out} rows and needs at least 2 f + 1 = "
+                         f"{2 * nb_decl_byz + 1} of them")
     if gar in _CENTER:
       # geomed: nu / iters / tol; cclip: tau (required) / iters / tol — checked here, not at the first step
       from . import gars
@@ -291,6 +332,11 @@ class AggregationStep:
     self.h = nb_workers - nb_real_byz
     self.gar = gar
     self.gar_args = dict(gar_args or {})
+    self.pre = pre
+    self.pre_args = pre_args if pre is not None else {}
+    self.pre_form = self.pre_args.get("form", "rows")
+    self.last_masks = None        # bucketing: the masks of the last step (int64[MAX_ROWS] where the rows live)
+    self._bucket_counter = None   # ... the draw's counter: a device int64[1] the kernel advances, or a Python integer
     self.mu = momentum
     self.damp = dampening
     self.omd = 1.0 - dampening
@@ -367,8 +413,20 @@ class AggregationStep:
     single = bool(single_call and fixed and not behind and self.momentum_at == "worker" and "step_worker" in caps
                   and gar in _DISTANCE + _COLWISE and only_m and (not self.agg.collective or self.agg.native is not None))
     accept = "count" if gar in _ACCEPT_COUNTED else ("average" if gar == "average" else None)
+    if self.pre is not None:
+      # a pre-aggregation stands in front of the rule: the rule never rides in the first pass, but the distance pass does
+      # wherever the pre-aggregated rule starts from the distances of the whole stack, whatever the rule and its gar_args
+      # (under the conditions of "sqdist" above: the chain of conditions before it is the same)
+      from_sq = self.pre == "nnm" or (self.pre_form == "scalars" and gar != "average")
+      if first_pass != "direction" and not behind:  # (the attack is formed in the first pass, at a fixed factor)
+        first_pass = "sqdist" if stem and k >= 1 and from_sq and stem + "sqdist" in caps else "plain"
+      if not fixed:
+        search = "generic"
+        device_cursor = self.line_search == "auto" and "device_search" in caps and gar != "brute"
+      single, accept = False, None
     return StepPlan(only_m, analytic, first_pass, search, device_cursor, single, caps, accept,
-                    searches=not fixed and k > 0, forms_vector=not behind or first_pass == "direction", attack=att)
+                    searches=not fixed and k > 0, forms_vector=not behind or first_pass == "direction", attack=att,
+                    pre=self.pre)
 
   # ------------------------------------------------------------------------ #
 
@@ -407,8 +465,38 @@ class AggregationStep:
     slower than separate allocations in every A/B, profiles/r03_h / r03_i, so the step keeps separate ones.)"""
     return [torch.zeros_like(like) if zero else torch.empty_like(like) for _ in range(count)]
 
-  def _aggregate(self, gradients):
+  def _draw_masks(self, like):
+    """bucketing: the masks of this run(), drawn before anything aggregates — from the device counter where the backend
+    has the leg and the rows are on a GPU (the kernel advances it), else from a host counter advanced here."""
+    s, seed, legs = self.pre_args["s"], self.pre_args.get("seed", 0), self.agg.legs
+    if "bucket_masks" in self.plan.capabilities and like.is_cuda:
+      if self._bucket_counter is None:
+        self._bucket_counter = torch.zeros(1, dtype=torch.int64, device=like.device)
+      self.last_masks = legs.bucket_masks(self.n, s, seed, self._bucket_counter, like)
+    else:
+      count = self._bucket_counter or 0
+      self.last_masks = legs.bucket_masks(self.n, s, seed, count, like)
+      self._bucket_counter = count + 1
+
+  def _aggregate_pre(self, gradients, local_sq):
+    """The rule behind the pre-aggregation (ShardedAggregator.nnm / .bucketing); local_sq: the squared distances of
+    `gradients` on this rank where the first pass formed them."""
+    agg, gar, args = self.agg, self.gar, dict(self.gar_args)
+    if gar == "brute":
+      args["check"] = True  # (as in _aggregate)
+    if gar == "cclip":
+      args["start"] = self.cclip_start
+    if self.pre == "nnm":
+      return agg.nnm(gradients, self.f_decl, rule=gar, form=self.pre_form, local_sq=local_sq, **args)
+    if pipelines.NNM_RULES[gar]:
+      args["f"] = self.f_decl
+    return agg.bucketing(gradients, self.pre_args["s"], gar, masks=self.last_masks, form=self.pre_form, local_sq=local_sq,
+                         **args)
+
+  def _aggregate(self, gradients, local_sq=None):
     agg, f = self.agg, self.f_decl
+    if self.pre is not None:
+      return self._aggregate_pre(gradients, local_sq)
     if self.gar == "median":
       return agg.median(gradients)
     if self.gar == "average":
@@ -597,6 +685,8 @@ class AggregationStep:
       raise ValueError(f"{len(sampled)} sampled gradients for {self.h} honest workers")
     if self.single_call:
       return self._run_single_call(sampled, len(sampled), self.omd, params, origin)
+    if self.pre == "bucketing":
+      self._draw_masks(sampled[0])
     factors = self._clip_factors(sampled)                   # 0.
     first = self._first_pass(sampled, factors)              # 1. and what it does of 2.
     byz = self._byzantine(first, sampled)                   # 2.
@@ -724,9 +814,9 @@ class AggregationStep:
     """Step 3 (attack.py:821): what the first pass fused, the rule from the distances it left, or the rule itself."""
     if first.fused_defense is not None:
       return first.fused_defense
-    if first.fused_sq is not None:
+    if first.fused_sq is not None and self.pre is None:
       return self.agg.rule_from_sq(self.gar, first.honests + attacks, first.fused_sq, self.f_decl, self.gar_args.get("m"))
-    defense = self._aggregate(first.honests + attacks)
+    defense = self._aggregate(first.honests + attacks, first.fused_sq)
     if self.gar == "cclip":
       self.cclip_start = defense  # the next step clips around this one's aggregate (never written again: no clone)
     return defense

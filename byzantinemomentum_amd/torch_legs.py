@@ -289,6 +289,16 @@ def _mix_rows_torch(rows, masks, n_out):
   return outs
 
 
+def _bucket_masks_torch(n, s, seed, counter, like):
+  """bm_bucket_masks for a backend without the leg: the counter-based permutation in Python integers
+  (gars.bucket_permutation) cut into buckets of s — int64[MAX_ROWS] where `like` lives, zeros beyond ceil(n / s).
+  `counter`: a Python integer (a host counter: whoever calls advances it)."""
+  from . import gars
+  words = gars.bucket_masks(n, s, gars.bucket_permutation(n, seed, counter))
+  words = [w - (1 << 64) if w >= (1 << 63) else w for w in words]
+  return torch.tensor(words + [0] * (_lib.MAX_ROWS - len(words)), dtype=torch.int64, device=like.device)
+
+
 def _mask_words(masks, count):
   return [int(w) & ((1 << 64) - 1) for w in masks[:count].tolist()]
 
@@ -382,11 +392,13 @@ def _declared_only(name):
 class Legs:
   """The compute legs of one backend as ShardedAggregator and pipelines call them, resolved ONCE: each optional leg is
   the backend's method where the backend declares the capability, else its stand-in above (`native` names the former).
-  `colwise_mixed` (a fusion, not a step) and `brute_select_device` (absent on the oracle backend) have no stand-in: None."""
+  `colwise_mixed` / `colwise_bucketed` (fusions, not steps) and `brute_select_device` (absent on the oracle backend) have
+  no stand-in: None."""
 
   STAND_INS = {"center_weights": _center_weights_torch, "spectral_weights": _spectral_weights_torch,
                "weighted_sum": _weighted_sum_torch, "nnm_masks": _nnm_masks_torch, "mix_rows": _mix_rows_torch,
-               "colwise_mixed": None, "mixed_sqdist": _mixed_sqdist_torch, "mix_weights": _mix_weights_torch,
+               "colwise_mixed": None, "colwise_bucketed": None, "bucket_masks": _bucket_masks_torch,
+               "mixed_sqdist": _mixed_sqdist_torch, "mix_weights": _mix_weights_torch,
                "attack_vector": _attack_vector_torch, "perturb_stats": _perturb_stats_torch,
                "minmax_factor": _minmax_factor_torch, "anticge": _anticge_torch}
   TAKE_THE_BACKEND = ("perturb_stats", "anticge")

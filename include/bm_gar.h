@@ -652,6 +652,36 @@ int bm_colwise_mixed(int op, const float* const* rows, int n, const uint64_t* ma
                      void* stream);
 int bm_colwise_mixed_max_rows(void);
 
+/* The same with n_out < n mixed rows — bucketing in front of the coordinate-wise median / trimmed mean without the
+ * bucket means.  out = rule(y_0 .. y_{n_out-1}), y_r the rows bm_mix_rows(rows, n, masks_dev, n_out) would write
+ * (masks_dev: at least n_out words, general 64-bit masks: they may overlap, an empty one gives a NaN row), for op =
+ * BM_OP_MEDIAN or BM_OP_TRMEAN (f: the trimmed mean's on the n_out rows, n_out >= 2 f + 1).  One pass, 4 d (n + 1) bytes
+ * where the two kernels move 4 d (n + 2 n_out + 1).  The same bits as bm_colwise on the rows bm_mix_rows writes: the
+ * sequential fp32 sum in ascending row order, one IEEE division by the popcount, a row outside a mask without influence
+ * on y_r even where it holds NaN or inf.  Instances exist for n_out = ceil(n / 2) and ceil(n / 3), n = 2 .. an internal
+ * limit per bucket size, decided by measurement: bm_colwise_bucketed_supported says 1 for those (op, n, n_out), 0
+ * otherwise; an
+ * unsupported shape returns BM_EINVAL and the caller runs bm_mix_rows and bm_colwise.  A null pointer, n_out outside
+ * 1 .. n, a bad f or d < 0: BM_EINVAL before any HIP call.  d == 0 launches nothing.  Joined ABI 23 (additions only). */
+int bm_colwise_bucketed_supported(int op, int n, int n_out);
+int bm_colwise_bucketed(int op, const float* const* rows, int n, const uint64_t* masks_dev, int n_out, int64_t d, int f,
+                        float* out, void* stream);
+
+/* Bucket masks from a counter (bucketing: Karimireddy, He, Jaggi, ICLR 2022): a permutation of 0 .. n-1 that is a
+ * function of (n, seed, counter) alone, cut into buckets of s.  All arithmetic is uint64 and wrapping:
+ *     mix(x):  x ^= x >> 30;  x *= 0xBF58476D1CE4E5B9;  x ^= x >> 27;  x *= 0x94D049BB133111EB;  x ^= x >> 31
+ *     u_i    = mix(seed + 0x9E3779B97F4A7C15 * (64 * counter + i))                      i = 1 .. n-1
+ *     perm   = (0 .. n-1);  for i = n-1 down to 1:  j = u_i mod (i + 1);  swap(perm[i], perm[j])
+ *     bucket b = { perm[b s] .. perm[min(n, b s + s) - 1] },  b < ceil(n / s);  masks[b] has bit j set iff j is in bucket b
+ * BM_MAX_ROWS words are written, zeros beyond ceil(n / s).  bm_bucket_masks: HOST function, host array, no stream.
+ * bm_bucket_masks_device: one wavefront reads counter_dev[0] (DEVICE), writes the masks of that counter (DEVICE) and
+ * stores counter + 1 back with an ordinary store, no atomic — the counter word belongs to one stream of launches — so a
+ * recorded graph draws the next permutation at every replay with no host involvement, and every rank of a sharded run
+ * draws the same one without a collective.  The same masks from both.  BM_EINVAL for a null pointer, n outside
+ * 1 .. BM_MAX_ROWS or s outside 1 .. n, before any HIP call.  Joined ABI 23 (additions only). */
+int bm_bucket_masks(int n, int s, uint64_t seed, uint64_t counter, uint64_t* masks_host);
+int bm_bucket_masks_device(int n, int s, uint64_t seed, uint64_t* counter_dev, uint64_t* masks_dev, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Distance-based rules on mixed rows WITHOUT the mixed rows.  These four entry points joined ABI 23: additions only.
  *
