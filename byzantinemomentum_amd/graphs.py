@@ -23,6 +23,20 @@ rules over torch.distributed collectives that stage through the host, and `Shard
 that has no device search (the HIP backend has one, bm_brute_select_device: its brute IS capturable; the status of
 the search stays on the device until `check_brute()` / `floats()`).  A failed recording raises GraphCaptureError and
 leaves nothing behind.
+
+A graphed `AggregationStep.run()` either IS the eager step at every replay or is refused, on the host, before anything
+is launched for it (step.AggregationStep.graph_refusal gives the reason, GraphedCall raises it as GraphCaptureError):
+  * what the step keeps from one step to the next must live where the recorded kernels read AND write it.  The momentum
+    buffers, the update-placement momentum and the bucketing counter do; the server momentum and cclip's start are
+    rebound to the newest defense vector by an eager step, so a step warmed up or recorded here keeps both in buffers of
+    its own, filled by one d-sized copy at the end of the step (the defense vector handed out is never written again);
+  * `floats()`, `last_factor` and `last_search` cache what they fetched; every replay advances `replay_epoch()`, which
+    those caches are keyed on, so they read the device again after a replay and not between two;
+  * refused: nb_past > 0 (the deque of past averages, the curvature mode 1 / 2 / 3 and the previous step's norm advance
+    in Python: a recording would freeze one of them); a factor search whose cursor is on the host (`line_search="host"`
+    / `"generic"`, Brute, Bulyan without the device ranking, and the scalar rules under empire-strict or with more than
+    62 honest rows: a read per evaluation, or one per search); bucketing on a backend without the device counter of
+    bm_bucket_masks_device (the draw's counter is then a Python integer).
 """
 
 import torch
@@ -33,7 +47,47 @@ __all__ = ["GraphedCall", "GraphCaptureError"]
 
 
 class GraphCaptureError(RuntimeError):
-  """`fn` could not be recorded into a HIP graph (it synchronised with the host, or a launch failed under capture)."""
+  """`fn` could not be recorded into a HIP graph (it synchronised with the host, a launch failed under capture, or a step
+  refused: GraphRefusal)."""
+
+
+class GraphRefusal(RuntimeError):
+  """Raised by a call that knows, on the host and before it launches anything, that a replay of it would not be the call
+  (step.AggregationStep.run with a configuration of graph_refusal())."""
+
+
+_replays = 0    # advanced by every replay of every GraphedCall: what host-side caches of device scalars are keyed on
+_preparing = 0  # GraphedCalls between their first warm-up call and the end of their recording
+
+
+def replay_epoch():
+  """A number that changes with every replay (notify_replay): a value fetched from device memory under one epoch says
+  nothing under the next."""
+  return _replays
+
+
+def notify_replay():
+  """What a replay tells the rest of the package: the recorded kernels may have written anything, so no ranking of
+  earlier contents (gars.py) and no scalar fetched earlier (step.AggregationStep.floats / last_factor / last_search)
+  survives."""
+  global _replays
+  gars.invalidate_rank_cache()
+  _replays += 1
+
+
+def capturing():
+  """Whether the current stream is recording; False in a process that has no GPU (where the runtime's own question
+  raises)."""
+  try:
+    return bool(torch.cuda.is_current_stream_capturing())
+  except RuntimeError:
+    return False
+
+
+def preparing():
+  """Whether a GraphedCall is warming its call up or recording it: a step that runs now keeps the state it carries from
+  step to step at addresses of its own (module docstring)."""
+  return _preparing > 0
 
 
 class GraphedCall:
@@ -44,8 +98,16 @@ class GraphedCall:
   the package that writes user tensors.  An eager rule after a replay ranks the contents it finds."""
 
   def __init__(self, fn, warmup=2):
+    global _preparing
     if not torch.cuda.is_available():
       raise RuntimeError("GraphedCall records HIP graphs: it needs the GPU the rows live on")
+    _preparing += 1
+    try:
+      self._prepare(fn, warmup)
+    finally:
+      _preparing -= 1
+
+  def _prepare(self, fn, warmup):
     self._graph = torch.cuda.CUDAGraph()
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
@@ -55,7 +117,11 @@ class GraphedCall:
       # "reuse the last ranking" (the graph would then hold the averaging kernel alone)
       for _ in range(max(int(warmup), 1)):
         gars.invalidate_rank_cache()
-        fn()
+        try:
+          fn()
+        except GraphRefusal as err:  # (decided before anything was launched: nothing to undo)
+          self._graph = None
+          raise GraphCaptureError(f"the call refuses to be recorded into a HIP graph: {err}") from err
     torch.cuda.current_stream().wait_stream(side)
     torch.cuda.synchronize()
     gars.invalidate_rank_cache()
@@ -82,6 +148,6 @@ class GraphedCall:
     self._stream = side
 
   def __call__(self):
-    gars.invalidate_rank_cache()  # (the recorded kernels may write anything: no ranking of earlier contents survives)
+    notify_replay()  # (the recorded kernels may write anything: no ranking, no fetched scalar of earlier contents survives)
     self._graph.replay()
     return self.output

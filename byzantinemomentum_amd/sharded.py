@@ -366,6 +366,7 @@ class ShardedAggregator:
         warnings.warn(f"libbm_gar RCCL communicator unavailable ({failure}); using torch.distributed collectives")
         self.single_call = False
     self.brute_status = None
+    self._identity = {}  # (n, device) -> the index table 0 .. n-1 of average()
     # (index tensor, count): the rows the latest krum / rule_from_sq("krum") / brute / aksel / cge of THIS aggregator
     # averaged are the first `count` entries of the tensor, which stays where the rule left it (device memory with the
     # HIP backend; after a single-call krum a view of the stream's workspace: read it on that stream before the next
@@ -612,7 +613,13 @@ class ShardedAggregator:
 
   def average(self, local):
     n = len(local)
-    return self.backend.selected_mean(local, self.backend.index_tensor(list(range(n)), local[0]), n)
+    # the table 0 .. n-1 is made once per (n, device): a copy from the host per call could not be recorded into a HIP
+    # graph (graphs.GraphedCall), and nobody writes it
+    key = (n, local[0].device)
+    table = self._identity.get(key)
+    if table is None:
+      table =self._identity[key] = self.backend.index_tensor(list(range(n)), local[0])
+    return self.backend.selected_mean(local, table, n)
 
   def cge(self, local, f):
     n = len(local)

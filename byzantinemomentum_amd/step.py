@@ -53,7 +53,7 @@ from typing import Any, NamedTuple, Optional
 
 import torch
 
-from . import _lib, linesearch, pipelines
+from . import _lib, graphs, linesearch, pipelines
 
 __all__ = ["AggregationStep"]
 
@@ -176,7 +176,16 @@ class _Pending:
   study: Any = None           # the slots of bm_study_stats
   prev_s2: Any = None         # device fp64[1]: |newest past average|^2
   accept: Any = None          # device fp64[1]: Byzantine rows among those the rule averaged
-  floats: Optional[dict] = None  # the study row, once fetched
+  floats: Optional[dict] = None  # the study row, once fetched ...
+  epoch: int = -1                # ... under this graphs.replay_epoch(): a replay rewrites the tensors above in place
+
+
+def _ieee_div(a, b):
+  """a / b as the reference's tensor division has it (attack.py:854-859): a zero divisor gives NaN or an infinity."""
+  try:
+    return a / b
+  except ZeroDivisionError:
+    return math.nan if a != a or a == 0 else math.copysign(math.inf, a) * math.copysign(1.0, b)
 
 
 class AggregationStep:
@@ -367,8 +376,16 @@ class AggregationStep:
     # cclip: the vector the clipping starts from, the previous step's defense vector (None before the first step: the
     # mean of the rows).  Advanced by _defense alone — the evaluations of a factor search read it and leave it
     self.cclip_start = None
+    # A step warmed up or recorded by graphs.GraphedCall (`_keeps_state`, from then on) keeps the server momentum and
+    # cclip's start in buffers of its own, filled by a copy at the end of the step: the recorded kernels then read what
+    # the replay before them wrote.  A step that is never graphed rebinds both, as the reference does, and copies nothing
+    self._keeps_state = False
+    self._kept = {}                   # "server" / "cclip" -> the buffer
+    self._search_dev = None           # the device search's result tensor once last_factor / last_search were fetched ...
+    self._search_epoch = -1           # ... under this graphs.replay_epoch()
     self.plan = self._make_plan(single_call)
     self.single_call = self.plan.single_call
+    self._refusal = self.graph_refusal()
 
   def _make_plan(self, single_call):
     """Every decision that depends on the constructor's arguments and the backend alone.  A backend names its optional
@@ -434,29 +451,40 @@ class AggregationStep:
   def last_factor(self):
     """The factor of the last step (the searched one with attack_evals).  After a device search this is the read that
     synchronises; a step that never looks costs nothing."""
+    self._unsettle_after_replay()
     if isinstance(self._factor_now, torch.Tensor) and isinstance(self._search_now, torch.Tensor):
       self._settle_search()
     return self._factor_now  # (minmax / minsum: the device tensor the chain left, handed out as it is)
 
   @last_factor.setter
   def last_factor(self, value):
-    self._factor_now = value
+    self._factor_now, self._search_dev = value, None
 
   @property
   def last_search(self):
     """[(x, objective)] of the last search, in evaluation order."""
+    self._unsettle_after_replay()
     if isinstance(self._search_now, torch.Tensor):
       self._settle_search()
     return self._search_now
 
   @last_search.setter
   def last_search(self, value):
-    self._search_now = value
+    self._search_now, self._search_dev = value, None
 
   def _settle_search(self):
-    values = self._fetch(self._search_now).tolist()
+    found = self._search_now
+    values = self._fetch(found).tolist()
     self._factor_now = values[0]
     self._search_now = [(values[1 + 2 * i], values[2 + 2 * i]) for i in range((len(values) - 1) // 2)]
+    self._search_dev, self._search_epoch = found, graphs.replay_epoch()
+
+  def _unsettle_after_replay(self):
+    """A replay of a recorded step runs the search again and leaves its result in the tensor the recording left: what
+    was fetched from it before describes an earlier step."""
+    if self._search_dev is not None and self._search_epoch != graphs.replay_epoch():
+      self._factor_now = self._search_now = self._search_dev
+      self._search_dev = None
 
   @staticmethod
   def _new_rows(count, like, zero=False):
@@ -673,6 +701,32 @@ class AggregationStep:
       self.ops.multi_fma3([params], [params], [mom], 1.0, -(self.mu * lr))
     return params
 
+  def graph_refusal(self):
+    """Why a replay of run() from a HIP graph (graphs.GraphedCall) would not be the step, or None: a replay runs the
+    recorded kernels and none of this file's Python.  run() raises graphs.GraphRefusal with it, before it launches
+    anything, while a GraphedCall warms the step up or a stream capture is in progress."""
+    plan = self.plan
+    if self.nb_past > 0:
+      return ("nb_past > 0: the deque of past sampled averages, the curvature mode and the previous step's norm advance "
+              "on the host, a recording would freeze one step's (use nb_past=0)")
+    if plan.searches and not plan.device_cursor:
+      return (f"the factor search's cursor is on the host (search {plan.search!r}, line_search={self.line_search!r}, "
+              f"rule {self.gar}, attack {self.attack}): it reads the device at every evaluation, or once per search")
+    if self.pre == "bucketing" and "bucket_masks" not in plan.capabilities:
+      return "bucketing on a backend without the device counter: the draw's counter is a Python integer"
+    return None
+
+  def _carried(self, key, vector):
+    """`vector` where the next step reads it: the vector itself, or — in a step a GraphedCall has warmed up or recorded
+    — this step's own buffer for `key` after one d-sized copy, an address the recorded kernels read and write alike."""
+    if not self._keeps_state:
+      return vector
+    own = self._kept.get(key)
+    if own is None or own.shape != vector.shape or own.device != vector.device:
+      own = self._kept[key] = torch.empty_like(vector)
+    own.copy_(vector)
+    return own
+
   def run(self, grad_sampleds, params=None, origin=None):
     """grad_sampleds: list of >= h flat fp32 GPU tensors (this rank's slice of the step's sampled
     gradients).  params/origin: optional flat parameter vectors for `l2_origin` (attack.py:830).
@@ -683,6 +737,11 @@ class AggregationStep:
       sampled = Shards(sampled, d_total=grad_sampleds.d_total)
     if len(sampled) < self.h:
       raise ValueError(f"{len(sampled)} sampled gradients for {self.h} honest workers")
+    warming = graphs.preparing()
+    if self._refusal is not None and (warming or graphs.capturing()):
+      raise graphs.GraphRefusal(f"this step cannot be replayed from a HIP graph: {self._refusal}")
+    if warming:
+      self._keeps_state = True
     if self.single_call:
       return self._run_single_call(sampled, len(sampled), self.omd, params, origin)
     if self.pre == "bucketing":
@@ -818,13 +877,14 @@ class AggregationStep:
       return self.agg.rule_from_sq(self.gar, first.honests + attacks, first.fused_sq, self.f_decl, self.gar_args.get("m"))
     defense = self._aggregate(first.honests + attacks, first.fused_sq)
     if self.gar == "cclip":
-      self.cclip_start = defense  # the next step clips around this one's aggregate (never written again: no clone)
+      # the next step clips around this one's aggregate (never written again: no clone; a graphed step keeps a copy)
+      self.cclip_start = self._carried("cclip", defense)
     return defense
 
   def _update_momentum(self, defense):
     """Step 4 (attack.py:832-839): what update_gradient() hands out."""
     if self.momentum_at == "server":
-      self.server_momentum = defense          # no clone, as attack.py:835
+      self.server_momentum = self._carried("server", defense)  # no clone, as attack.py:835 (a graphed step: a copy)
       self._update = defense
     elif self.momentum_at == "update":
       # M <- mu * M + (1 - damp) * defense (attack.py:836-838) rides along with the study block, which reads the defense
@@ -953,7 +1013,8 @@ class AggregationStep:
     def cos(i, j):
       if not att and 3 in (i, j):  # (no attack: no fourth vector)
         return nan
-      return g[4 * i + j] / math.sqrt(g[5 * i]) / math.sqrt(g[5 * j])
+      # (a vector of norm 0 — empire at a factor that cancels the average — divides like the reference's tensors: NaN)
+      return _ieee_div(_ieee_div(g[4 * i + j], math.sqrt(g[5 * i])), math.sqrt(g[5 * j]))
 
     past = pend.npast > 0
     if self.plan.accept == "count":  # the reference's own `count / m`, int / int (krum.py:144-151 and its likes)
@@ -969,19 +1030,23 @@ class AggregationStep:
       "defense_norm_avg": math.sqrt(rec.d2), "defense_norm_max": rec.dmax,
       "cosin_splhon": cos(0, 1), "cosin_spldef": cos(0, 2), "cosin_hondef": cos(1, 2),
       "cosin_splatt": cos(0, 3), "cosin_honatt": cos(1, 3), "cosin_attdef": cos(3, 2),
-      "cosin_sampled": rec.ex0 / math.sqrt(rec.s2) / math.sqrt(rec.prev_s2) if past else nan,
+      "cosin_sampled": _ieee_div(_ieee_div(rec.ex0, math.sqrt(rec.s2)), math.sqrt(rec.prev_s2)) if past else nan,
       "curv_sampled": self.mu * rec.ex1 if past else nan,
       "accept_ratio": accept,
     }
 
   def floats(self):
     """Python floats of the study row (attack.py:822,828-868) for the last run(); synchronises once.
-    Idempotent: a second call returns the same dictionary without touching the device."""
+    Idempotent: a second call returns the same dictionary without touching the device — until a HIP graph is replayed
+    (graphs.replay_epoch): a replay of this step rewrites the scalars where they are and creates no record, so the row
+    is fetched again."""
     pend = self._pending
     if pend is None:
       raise RuntimeError("floats() needs a run() first")
-    if pend.floats is None:
+    epoch = graphs.replay_epoch()
+    if pend.floats is None or pend.epoch != epoch:
       if self.gar == "brute":
         self.agg.check_brute()  # (a step replayed from a HIP graph could not check inside run(): here at the latest)
       pend.floats = self._study_floats(self._unpack(pend) if pend.packed is not None else self._exchange(pend), pend)
+      pend.epoch = epoch
     return pend.floats

@@ -94,12 +94,17 @@ def gar_args(case):
   return args
 
 
+def nb_past_of(case):
+  """NB_PAST, or what a case that carries an `nb_past` of its own says (tests/graph_matrix.py: 0)."""
+  return getattr(case, "nb_past", NB_PAST)
+
+
 def constructor_kwargs(case):
   """The keyword arguments of AggregationStep for a case (all but the aggregator)."""
   att = ATTACK[case.attack]
   return dict(nb_workers=case.n, nb_decl_byz=case.f_decl, nb_real_byz=case.f_real, gar=case.rule, gar_args=gar_args(case),
               momentum=MU, dampening=DAMP, momentum_at=case.placement, attack=att.name, attack_factor=case.factor,
-              nb_past=NB_PAST, gradient_clip=case.clip, single_call=case.single_call, attack_args=att.args)
+              nb_past=nb_past_of(case), gradient_clip=case.clip, single_call=case.single_call, attack_args=att.args)
 
 
 def sampled_rows(seed, it, count, d):
@@ -334,7 +339,7 @@ class MatrixLoop(Loop):
   purpose (tests/test_step_matrix_cpu.py shows that the comparison catches each)."""
 
   def __init__(self, case, twin=None):
-    super().__init__(case.n, case.f_decl, case.f_real, case.rule, case.placement, MU, DAMP, case.clip, NB_PAST)
+    super().__init__(case.n, case.f_decl, case.f_real, case.rule, case.placement, MU, DAMP, case.clip, nb_past_of(case))
     self.case, self.att, self.twin = case, ATTACK[case.attack], twin
     self.args = gar_args(case)
     self.start = None      # cclip: the previous defense
